@@ -3,8 +3,18 @@ packets (BASELINE.json metric, configs[1] at N=1; configs[3]'s per-GPU shard
 at N>1).  One step = one ebpf_exec_batch of the loaded xdp-counter bytecode
 over the whole resident batch (2^24 packets per GPU).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--full adds what the headline figure does not need: the parity checks of the
+timed run, the host-memory (e2e) leg and the CPU baseline (the last two can
+still be switched off there with --no-e2e / --no-cpu-baseline).  The
+secondary workloads (--workload) always check their own parity; their CPU
+baseline leg also waits for --full.
+
+--dump-outputs DIR writes what the last timed step left for its caller as
+DIR/<name>.npy (dump_outputs below).
 
 Prints ONE JSON line on rank 0.
 """
@@ -39,7 +49,20 @@ def parse():
     ap.add_argument("--no-e2e", action="store_true", help="skip the host-memory (PCIe-inclusive) leg")
     ap.add_argument("--e2e-chunk-log2", type=int, default=20, help="packets per H2D chunk = 2^k")
     ap.add_argument("--e2e-streams", type=int, default=3, help="streams the host-memory leg rotates over")
+    ap.add_argument("--full", action="store_true", default=os.environ.get("BPFTIME_AMD_BENCH_FULL") == "1",
+                    help="also run what the headline figure does not need: parity checks of the timed run, "
+                         "the host-memory leg, the CPU baseline (BPFTIME_AMD_BENCH_FULL=1 does the same for "
+                         "every line a script runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (headline workload)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.workload != "xdp-counter":
+        ap.error("--dump-outputs covers the headline workload (xdp-counter)")
+    if not args.full:
+        args.no_cpu_baseline = True
+        args.no_e2e = True
     args.log2n_set = args.log2n is not None
     if args.log2n is None:
         args.log2n = 24
@@ -118,19 +141,14 @@ def main():
     wall = t1 - t0
     kern_avg_s = ev0.elapsed_ms(ev1) / args.steps / 1e3
 
-    # ---- parity of the timed run (size-independent properties) ----
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, n, verd, pkts, bss)
+
+    # ---- parity of the timed run (size-independent properties; --full) ----
     total_runs = args.warmup + args.steps
-    v = verd.download(np.uint32)
-    ok_verdicts = bool((v == isa.XDP_TX).all())
-    cnt = np.frombuffer(bss.lookup(b"\0\0\0\0"), dtype=np.uint64)
-    ok_counter = int(cnt[0]) == total_runs * n and not cnt[1:].any()
-    sample = min(n, 1 << 16)
-    ref = gen.xdp_packets(sample, PKT, gen.SEED_CFG2, first)
-    got = pkts.download(count=sample * PKT).reshape(sample, PKT)
-    exp = ref.copy()
-    if total_runs % 2:
-        exp[:, :6], exp[:, 6:12] = ref[:, 6:12], ref[:, :6]
-    ok_bytes = bool((got == exp).all())
+    ok_verdicts = ok_counter = ok_bytes = None
+    if args.full:
+        ok_verdicts, ok_counter, ok_bytes = check_parity(dev, gen, isa, n, first, total_runs, verd, pkts, bss)
 
     shard = bss.snapshot()
     e2e = None
@@ -148,9 +166,12 @@ def main():
         rz.close()
         return
 
-    merged = merge_counter_shards(init_bss, shards)
-    merged_cnt = int(merged.view(np.uint64)[0])
-    parity = all(oks) and merged_cnt == world * total_runs * n
+    parity = None
+    if args.full:
+        merged = merge_counter_shards(init_bss, shards)
+        merged_cnt = int(merged.view(np.uint64)[0])
+        parity = {"verdicts_all_tx": ok_verdicts, "counter_exact": ok_counter, "mac_swap_sample": ok_bytes,
+                  "merged_counter": merged_cnt, "ok": all(oks) and merged_cnt == world * total_runs * n}
 
     tmax = max(times)
     value = world * n * args.steps / tmax / 1e6
@@ -194,8 +215,7 @@ def main():
             "interp": {"stack_bytes_per_lane": info["stack_size"], "fused_rmw": info["fused_rmw"],
                        "checked": not args.unchecked},
         },
-        "parity": {"verdicts_all_tx": ok_verdicts, "counter_exact": ok_counter, "mac_swap_sample": ok_bytes,
-                   "merged_counter": merged_cnt, "ok": parity},
+        "parity": parity,
         "roofline": {
             "bound": "hbm",
             "achieved": round(achieved_gbs, 2),
@@ -214,6 +234,70 @@ def main():
     print(json.dumps(out))
     if rz:
         rz.close()
+
+
+def check_parity(dev, gen, isa, n, first, total_runs, verd, pkts, bss):
+    """(verdicts all XDP_TX, counter == runs x n, MACs of the first 2^16
+    frames swapped runs times) after `total_runs` launches over the batch."""
+    import numpy as np
+    v = verd.download(np.uint32)
+    ok_verdicts = bool((v == isa.XDP_TX).all())
+    cnt = np.frombuffer(bss.lookup(b"\0\0\0\0"), dtype=np.uint64)
+    ok_counter = int(cnt[0]) == total_runs * n and not cnt[1:].any()
+    sample = min(n, 1 << 16)
+    ref = gen.xdp_packets(sample, PKT, gen.SEED_CFG2, first)
+    got = pkts.download(count=sample * PKT).reshape(sample, PKT)
+    exp = ref.copy()
+    if total_runs % 2:
+        exp[:, :6], exp[:, 6:12] = ref[:, 6:12], ref[:, :6]
+    ok_bytes = bool((got == exp).all())
+    return ok_verdicts, ok_counter, ok_bytes
+
+
+DUMP_SEED = 0x5EED0D0
+DUMP_BLOCK = 1024            # consecutive units per sampled block
+DUMP_VERDICT_BLOCKS = 1024   # 2^20 verdicts: 4 MiB as float32
+DUMP_PACKET_BLOCKS = 64      # 2^16 frames x 64 B: 16 MiB as float32
+
+
+def dump_blocks(n, nblocks):
+    """First units of `nblocks` blocks of DUMP_BLOCK consecutive units out of
+    n, ascending: every block when n has no more, else a seeded choice that
+    depends on n alone."""
+    import numpy as np
+    total = (n + DUMP_BLOCK - 1) // DUMP_BLOCK
+    if total <= nblocks:
+        return [b * DUMP_BLOCK for b in range(total)]
+    pick = np.random.default_rng(DUMP_SEED).choice(total, size=nblocks, replace=False)
+    return [int(b) * DUMP_BLOCK for b in np.sort(pick)]
+
+
+def dump_outputs(path, rank, world, n, verd, pkts, bss):
+    """What a caller of the timed ebpf_exec_batch holds after the last step,
+    as float32 / float64 .npy files under `path` (about 20 MiB):
+      verdicts.npy  the XDP verdict of the units in dump_blocks(n, 1024), float32
+      packets.npy   the rewritten frames (rows of 64 bytes) of the units in
+                    dump_blocks(n, 64), float32
+      counters.npy  the program's .bss map value as 512 u64 counters, float64
+                    (exact below 2^53)
+    The input frames are the seeded generator's and the sample depends on n
+    alone, so two builds run with the same arguments write comparable files.
+    A rank of a multi-GPU run writes <name>.rank<r>.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    sfx = "" if world == 1 else ".rank%d" % rank
+
+    def units(buf, dtype, width, nblocks):
+        item = np.dtype(dtype).itemsize * width
+        parts = [buf.download(dtype, count=min(DUMP_BLOCK, n - u) * width, offset=u * item)
+                 for u in dump_blocks(n, nblocks)]
+        return np.concatenate(parts).astype(np.float32)
+
+    np.save(os.path.join(path, "verdicts%s.npy" % sfx), units(verd, np.uint32, 1, DUMP_VERDICT_BLOCKS))
+    np.save(os.path.join(path, "packets%s.npy" % sfx),
+            units(pkts, np.uint8, PKT, DUMP_PACKET_BLOCKS).reshape(-1, PKT))
+    np.save(os.path.join(path, "counters%s.npy" % sfx),
+            np.frombuffer(bss.lookup(b"\0\0\0\0"), dtype=np.uint64).astype(np.float64))
 
 
 def gather_ranks(rz, world, payload):

@@ -3,7 +3,6 @@ GPU: parsing, libbpf-style map / global-data relocation and CO-RE against
 the xdp_md layout of runtime/extension/userspace_xdp.h:6-17, checked
 instruction by instruction and, through the oracle, against the
 hand-assembled xdp-counter of SURVEY.md Appendix A on the config-1 pcap."""
-import os
 import struct
 
 import numpy as np
@@ -14,8 +13,6 @@ from bpftime_amd.object import BpfObject, ObjectError
 
 import _elf
 from _helpers import make_maps
-
-BASE_BTF = "/root/reference/example/xdp-counter/base.btf"  # present only in the build container
 
 
 def decode(code: bytes):
@@ -54,12 +51,12 @@ def test_relocated_instructions(variant):
         assert ins[i] == raw[i], i
 
 
-@pytest.mark.skipif(not os.path.exists(BASE_BTF), reason="reference tree not mounted (GPU box)")
-def test_reference_base_btf_gives_builtin_layout():
-    """The reference example's base.btf (its xdp_md: u64 data / data_end)
-    relocates exactly like the built-in target."""
+def test_target_btf_gives_builtin_layout():
+    """A target BTF that lays xdp_md out as the reference example's base.btf
+    does (u64 data / data_end; built by _elf.target_btf_xdp_md) relocates
+    exactly like the built-in target."""
     o1 = BpfObject.from_bytes(_elf.xdp_counter_object(), "xdp-counter")
-    o2 = BpfObject.from_bytes(_elf.xdp_counter_object(), "xdp-counter", btf=open(BASE_BTF, "rb").read())
+    o2 = BpfObject.from_bytes(_elf.xdp_counter_object(), "xdp-counter", btf=_elf.target_btf_xdp_md())
     assert o1.insns(0, [3, 4]) == o2.insns(0, [3, 4])
 
 

@@ -1,3 +1,4 @@
+export BPFTIME_AMD_BENCH_FULL=1   # every bench.py line below runs as with --full (parity, e2e and CPU legs)
 # A/B of an environment switch over bench lines on one box, alternating:
 #   VAR=BPFTIME_AMD_LANE_PAD VALS="1 0" WL="tail-call flow-hash" REPS=2 bash tools/ab_env_lines.sh
 set -o pipefail

@@ -1,4 +1,5 @@
 #!/bin/bash
+export BPFTIME_AMD_BENCH_FULL=1   # every bench.py line below runs as with --full (parity, e2e and CPU legs)
 # Every bench line once (the headline with its CPU baseline and e2e leg), JSON
 # lines to gpurun_out/bench_<workload>.json
 set -u

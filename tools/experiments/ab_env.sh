@@ -1,4 +1,5 @@
 #!/bin/bash
+export BPFTIME_AMD_BENCH_FULL=1   # every bench.py line below runs as with --full (parity, e2e and CPU legs)
 # one build, several environments: bash tools/experiments/ab_env.sh build workload "ENV1" "ENV2" ...
 set -u
 v=$1; w=$2; shift 2

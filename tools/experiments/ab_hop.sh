@@ -1,4 +1,5 @@
 #!/bin/bash
+export BPFTIME_AMD_BENCH_FULL=1   # every bench.py line below runs as with --full (parity, e2e and CPU legs)
 # A/B of the dispatch table's branch hop (gen_fast.py BPFTIME_AMD_EXTRA_HOP, at commit aabfa90:
 # the knob went with the table when dispatch became direct, 54c3d9e):
 # the default library against one built with a second branch per dispatch

@@ -1,4 +1,5 @@
 #!/bin/bash
+export BPFTIME_AMD_BENCH_FULL=1   # every bench.py line below runs as with --full (parity, e2e and CPU legs)
 # Same-box A/B of two builds of libbpftime_amd.so, alternating, every bench
 # line without CPU legs:  tools/experiments/ab_lib.sh <tag> <lib A> <lib B>
 # (a path "default" = the in-tree library)

@@ -1,4 +1,5 @@
 #!/bin/bash
+export BPFTIME_AMD_BENCH_FULL=1   # every bench.py line below runs as with --full (parity, e2e and CPU legs)
 # SQ counters of the headline kernel for library builds under ab/: bash tools/experiments/ab_pmc.sh variant...
 set -u
 mkdir -p gpurun_out

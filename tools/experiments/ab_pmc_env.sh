@@ -1,4 +1,5 @@
 #!/bin/bash
+export BPFTIME_AMD_BENCH_FULL=1   # every bench.py line below runs as with --full (parity, e2e and CPU legs)
 # SQ counters of one workload under several environments: bash tools/experiments/ab_pmc_env.sh build workload "ENV1" "ENV2"
 set -u
 export TMPDIR=/tmp

@@ -1,4 +1,5 @@
 #!/bin/bash
+export BPFTIME_AMD_BENCH_FULL=1   # every bench.py line below runs as with --full (parity, e2e and CPU legs)
 # GPU suite, then same-box A/B of 1024-lane blocks (default for G launches)
 # against 256-lane blocks (BPFTIME_AMD_BLOCK=256) on the table workloads
 set -o pipefail

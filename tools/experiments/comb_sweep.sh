@@ -1,4 +1,5 @@
 #!/bin/bash
+export BPFTIME_AMD_BENCH_FULL=1   # every bench.py line below runs as with --full (parity, e2e and CPU legs)
 # Kernel time of one workload per combining-table size (BPFTIME_AMD_COMB_ENTRIES; "auto": the library's choice):
 #   bash tools/experiments/comb_sweep.sh <workload> "<entries...>" [extra env]
 set -u

@@ -1,3 +1,4 @@
+export BPFTIME_AMD_BENCH_FULL=1   # every bench.py line below runs as with --full (parity, e2e and CPU legs)
 mkdir -p gpurun_out
 timeout -k 10 120 python -u -m pytest tests/test_gpu_chain.py -x -q --timeout 60 --timeout-method thread -p no:cacheprovider > gpurun_out/g1_chain.log 2>&1 || { tail -5 gpurun_out/g1_chain.log; exit 1; }
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread -p no:cacheprovider > gpurun_out/g1_pytest.log 2>&1; rc=$?; tail -3 gpurun_out/g1_pytest.log; [ $rc -le 1 ] || exit $rc

@@ -1,4 +1,5 @@
 #!/bin/bash
+export BPFTIME_AMD_BENCH_FULL=1   # every bench.py line below runs as with --full (parity, e2e and CPU legs)
 # Headline kernel time per grid multiplier (BPFTIME_AMD_GRID_MULT; resident blocks x mult):
 #   bash tools/experiments/grid_sweep.sh "<mults...>"
 set -u

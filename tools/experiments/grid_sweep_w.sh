@@ -1,4 +1,5 @@
 #!/bin/bash
+export BPFTIME_AMD_BENCH_FULL=1   # every bench.py line below runs as with --full (parity, e2e and CPU legs)
 # One bench workload per grid multiplier (BPFTIME_AMD_GRID_MULT):
 #   bash tools/experiments/grid_sweep_w.sh <workload> "<mults...>"
 set -u

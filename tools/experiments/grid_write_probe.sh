@@ -1,4 +1,5 @@
 #!/bin/bash
+export BPFTIME_AMD_BENCH_FULL=1   # every bench.py line below runs as with --full (parity, e2e and CPU legs)
 # Headline per grid multiplier: bench time and the median launch's
 # WRITE_SIZE / FETCH_SIZE per packet (raw KiB counters, 2^24 packets)
 #   bash tools/experiments/grid_write_probe.sh "<mults...>"

@@ -1,4 +1,5 @@
 #!/bin/bash
+export BPFTIME_AMD_BENCH_FULL=1   # every bench.py line below runs as with --full (parity, e2e and CPU legs)
 # latency / occupancy PMC passes (rocprofv3 derived metrics, one per pass)
 # of one bench workload: bash tools/experiments/lat_pmc.sh <workload> [tag]
 set -u

@@ -1,4 +1,5 @@
 #!/bin/bash
+export BPFTIME_AMD_BENCH_FULL=1   # every bench.py line below runs as with --full (parity, e2e and CPU legs)
 # rocprofv3 passes for the headline bench (kernel-trace stats, then separate
 # PMC passes as MI355X_MICROARCH.md §rocprofv3 prescribes).
 set -u

@@ -1,4 +1,5 @@
 #!/bin/bash
+export BPFTIME_AMD_BENCH_FULL=1   # every bench.py line below runs as with --full (parity, e2e and CPU legs)
 # quick GPU iteration: parity tests, bench, one SQ counter pass
 set -u
 mkdir -p gpurun_out

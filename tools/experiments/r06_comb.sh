@@ -1,3 +1,4 @@
+export BPFTIME_AMD_BENCH_FULL=1   # every bench.py line below runs as with --full (parity, e2e and CPU legs)
 # round 6 layout checks: GPU suite, then bench lines and their LDS counters
 # (kt + SQ passes: SQ_LDS_BANK_CONFLICT, SQ_INSTS_LDS).  TAG names the run.
 set -o pipefail

@@ -1,3 +1,4 @@
+export BPFTIME_AMD_BENCH_FULL=1   # every bench.py line below runs as with --full (parity, e2e and CPU legs)
 # thread-ordered kernel, asm tier: tier / ORDERED diffs vs the oracle, the GPU
 # suite, the per-region profile (ab/seqprof.so) and the dispatch timings
 set -o pipefail

@@ -1,3 +1,4 @@
+export BPFTIME_AMD_BENCH_FULL=1   # every bench.py line below runs as with --full (parity, e2e and CPU legs)
 # the asm HASH-update handler: GPU suite, the thread-ordered timings and
 # profile, and every bench line's parity / time (no CPU legs)
 set -o pipefail

@@ -1,3 +1,4 @@
+export BPFTIME_AMD_BENCH_FULL=1   # every bench.py line below runs as with --full (parity, e2e and CPU legs)
 set -u
 for w in main flow-hash syscall-agg tail-call lpm-route ringbuf-sample; do
   if [ $w = main ]; then a=""; else a="--workload $w"; fi

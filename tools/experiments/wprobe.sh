@@ -1,4 +1,5 @@
 #!/bin/bash
+export BPFTIME_AMD_BENCH_FULL=1   # every bench.py line below runs as with --full (parity, e2e and CPU legs)
 # One bench line's raw WRITE_SIZE / FETCH_SIZE per unit of the median
 # interpreter launch under several environments (write attribution):
 #   bash tools/experiments/wprobe.sh <workload> <units> "ENV1" "ENV2" ...   ("X=1": none)

@@ -1,3 +1,4 @@
+export BPFTIME_AMD_BENCH_FULL=1   # every bench.py line below runs as with --full (parity, e2e and CPU legs)
 set -o pipefail
 export TMPDIR=/tmp
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > gpurun_out/fs_smoke.log 2>&1 || { tail -20 gpurun_out/fs_smoke.log; exit 1; }

@@ -1,3 +1,4 @@
+export BPFTIME_AMD_BENCH_FULL=1   # every bench.py line below runs as with --full (parity, e2e and CPU legs)
 # N=1 and N=2/4 (ranks sharing the box's one GPU) bench lines: the same HIP
 # runtime at every rank count (bench.py's file rendezvous, no torch import)
 set -o pipefail

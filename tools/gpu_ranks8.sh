@@ -1,3 +1,4 @@
+export BPFTIME_AMD_BENCH_FULL=1   # every bench.py line below runs as with --full (parity, e2e and CPU legs)
 # configs[3] rehearsal on one GPU: 8 ranks x 2^24 packets = 128M packets
 # through bench.py's file rendezvous and host merge (the driver's N=8 run
 # uses 8 GPUs; here the ranks share the box's one GPU, so the rate is the
