@@ -86,6 +86,7 @@ constexpr uint32_t MT_PERCPU_ARRAY = 6;
 constexpr uint32_t MT_LRU_HASH = 9;
 constexpr uint32_t MT_LPM_TRIE = 11;
 constexpr uint32_t MT_RINGBUF = 27;
+constexpr uint32_t MT_BLOOM_FILTER = 30;
 
 // Device-side map descriptor (64 B), indexed by fd.
 //   ARRAY          data = value_size * max_entries, stride value_size
@@ -111,6 +112,11 @@ constexpr uint32_t MT_RINGBUF = 27;
 //                  child[2], prefix data at key_off = 16, value at val_off};
 //                  read-only except in ORDERED batches of a program that
 //                  updates / deletes (dev_helpers.hpp lpm_update)
+//   BLOOM_FILTER   data = the bit array, (mask + 1) / 8 bytes, bit i in byte
+//                  i / 8 at bit i % 8 (bloom_filter.cpp:262-281); key_size 0;
+//                  nbuckets = mask (bits - 1, a power of two minus one),
+//                  slot_size = nr_hashes (1..15), key_off = the jhash seed
+//                  (bloom_mask / bloom_hashes / bloom_seed below)
 struct DMap {
   uint32_t type;
   uint32_t key_size;
@@ -127,6 +133,61 @@ struct DMap {
   uint64_t ix;          // device address of the u32 lookup index, 0 = not valid (LPM_TRIE: its flat table)
 };
 static_assert(sizeof(DMap) == 64, "DMap must be 64 bytes");
+
+// BLOOM_FILTER (runtime/src/bpf_map/userspace/bloom_filter.cpp).  The DMap
+// fields a Bloom filter reuses:
+inline BA_HD uint32_t bloom_mask(const DMap &m) { return m.nbuckets; }
+inline BA_HD uint32_t bloom_hashes(const DMap &m) { return m.slot_size; }
+inline BA_HD uint32_t bloom_seed(const DMap &m) { return m.key_off; }
+// Bit array size (bloom_filter.cpp:73-122): max_entries * nr_hashes * 7 / 5
+// bits, at least 64, at most 2^31, rounded up to a power of two.
+inline BA_HD uint64_t bloom_bits(uint32_t max_entries, uint32_t nr_hashes) {
+  uint64_t want = (uint64_t)max_entries * nr_hashes * 7 / 5;
+  if (want < 64) want = 64;
+  if (want > (1ull << 31)) want = 1ull << 31;
+  uint64_t bits = 1;
+  while (bits < want) bits <<= 1;
+  return bits;
+}
+// jhash (bloom_filter.cpp:125-228: Jenkins lookup3 hashlittle over bytes) on
+// the value as little-endian words, zero-padded to a multiple of 12 bytes:
+// the byte-wise tail adds exactly the bytes a zero-padded word holds.
+#define BA_ROL(x, k) (((x) << (k)) | ((x) >> (32 - (k))))
+#define BA_JMIX(a, b, c)                      \
+  {                                           \
+    a -= c; a ^= BA_ROL(c, 4); c += b;        \
+    b -= a; b ^= BA_ROL(a, 6); a += c;        \
+    c -= b; c ^= BA_ROL(b, 8); b += a;        \
+    a -= c; a ^= BA_ROL(c, 16); c += b;       \
+    b -= a; b ^= BA_ROL(a, 19); a += c;       \
+    c -= b; c ^= BA_ROL(b, 4); b += a;        \
+  }
+#define BA_JFINAL(a, b, c)                    \
+  {                                           \
+    c ^= b; c -= BA_ROL(b, 14);               \
+    a ^= c; a -= BA_ROL(c, 11);               \
+    b ^= a; b -= BA_ROL(a, 25);               \
+    c ^= b; c -= BA_ROL(b, 16);               \
+    a ^= c; a -= BA_ROL(c, 4);                \
+    b ^= a; b -= BA_ROL(a, 14);               \
+    c ^= b; c -= BA_ROL(b, 24);               \
+  }
+inline BA_HD uint32_t bloom_jhash_words(const uint32_t *w, uint32_t length, uint32_t initval) {
+  uint32_t a, b, c;
+  a = b = c = 0xdeadbeefu + length + initval;
+  for (; length > 12; length -= 12, w += 3) {
+    a += w[0];
+    b += w[1];
+    c += w[2];
+    BA_JMIX(a, b, c)
+  }
+  if (length == 0) return c;
+  a += w[0];
+  b += w[1];
+  c += w[2];
+  BA_JFINAL(a, b, c)
+  return c;
+}
 
 // Hash-map lookup index.  bpftime_hash_map's linear probing (kept as the
 // storage layout, so get_next_key walks buckets in the reference's order)

@@ -1140,6 +1140,135 @@ __device__ __forceinline__ DMap load_dmap(const DMap *maps, uint64_t fd) {
   return maps[fd];
 }
 
+// ---------------------------------------------------------------------------
+// BLOOM_FILTER (bloom_filter.cpp): bpf_map_push_elem / bpf_map_peek_elem
+// (helpers 87 / 89, bpf_helper.cpp:410-429).  A probe is the bit jhash(value,
+// value_size, seed + i) & mask of the array, i < nr_hashes; the bits live in
+// 32-bit words read with agent-scope loads and set with agent-scope atomic
+// ORs.  A bit is never cleared while a launch runs, so a word read from an
+// XCD's L2 that another XCD's push has since changed only misses bits: a
+// parallel batch's peek answers for some array between the one before the
+// batch and the final one.  ORDERED batches (`coh`) read at the coherence
+// point, where the one lane's earlier ORs were performed.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kBloomMaxHashes = 15;  // map_extra & 0xF
+constexpr uint32_t kBloomRegWords = 12;   // values of up to 48 bytes are hashed from registers
+
+// Word i of the value as jhash sees it (little-endian, zero past the value's
+// end), from a flat address of any alignment (a lane's stack, packet bytes).
+__device__ __forceinline__ uint32_t bloom_value_word(uint64_t v, uint32_t i, uint32_t vs) {
+  const uint32_t off = 4 * i;
+  if (off + 4 <= vs) return *(const u32u *)(v + off);
+  uint32_t w = 0;
+  for (uint32_t j = 0; j < 3; j++)
+    if (off + j < vs) w |= (uint32_t)(*(const volatile uint8_t *)(v + off + j)) << (8 * j);
+  return w;
+}
+
+struct BloomVal {
+  uint32_t w[kBloomRegWords];
+};
+
+// common.hpp bloom_jhash_words over the value's words held in registers: the
+// value size is wave-uniform (scalar branches), every index a constant
+__device__ __forceinline__ uint32_t bloom_hash_reg(const BloomVal &x, uint32_t vs, uint32_t initval) {
+  uint32_t a, b, c;
+  a = b = c = 0xdeadbeefu + vs + initval;
+  uint32_t t0 = x.w[0], t1 = x.w[1], t2 = x.w[2];  // the last (partial or whole) 12 bytes
+#pragma unroll
+  for (uint32_t blk = 0; blk + 1 < kBloomRegWords / 3; blk++) {
+    if (vs > 12 * (blk + 1)) {
+      a += x.w[3 * blk];
+      b += x.w[3 * blk + 1];
+      c += x.w[3 * blk + 2];
+      BA_JMIX(a, b, c)
+      t0 = x.w[3 * blk + 3];
+      t1 = x.w[3 * blk + 4];
+      t2 = x.w[3 * blk + 5];
+    }
+  }
+  a += t0;
+  b += t1;
+  c += t2;
+  BA_JFINAL(a, b, c)
+  return c;
+}
+
+// ... and for longer values, from memory on every probe
+__device__ __forceinline__ uint32_t bloom_hash_mem(uint64_t v, uint32_t vs, uint32_t initval) {
+  uint32_t a, b, c, i = 0, rem = vs;
+  a = b = c = 0xdeadbeefu + vs + initval;
+  for (; rem > 12; rem -= 12, i += 3) {
+    a += bloom_value_word(v, i, vs);
+    b += bloom_value_word(v, i + 1, vs);
+    c += bloom_value_word(v, i + 2, vs);
+    BA_JMIX(a, b, c)
+  }
+  a += bloom_value_word(v, i, vs);
+  b += bloom_value_word(v, i + 1, vs);
+  c += bloom_value_word(v, i + 2, vs);
+  BA_JFINAL(a, b, c)
+  return c;
+}
+
+// push (PUSH: sets the value's bits, returns 0) or peek (0 when every bit is
+// set, else -1; never writes *value).  Three passes, each unrolled over the
+// 15 possible probes under the wave-uniform nr_hashes: the bit positions,
+// then every word load, then the tests -- so the loads are all in flight
+// before the first is waited for.  A push issues an atomic OR only for a bit
+// its load found clear: a hot value costs loads, not atomics.
+template <bool PUSH>
+__device__ __forceinline__ uint64_t bloom_probe(const DMap &m, uint64_t value, bool coh) {
+  const uint32_t vs = m.value_size, k = bloom_hashes(m), seed = bloom_seed(m), mask = bloom_mask(m);
+  uint32_t pos[kBloomMaxHashes], word[kBloomMaxHashes];
+  if (vs <= 4 * kBloomRegWords) {
+    BloomVal x;
+#pragma unroll
+    for (uint32_t i = 0; i < kBloomRegWords; i++) x.w[i] = bloom_value_word(value, i, vs);
+#pragma unroll
+    for (uint32_t i = 0; i < kBloomMaxHashes; i++) pos[i] = i < k ? bloom_hash_reg(x, vs, seed + i) & mask : 0;
+  } else {
+#pragma unroll
+    for (uint32_t i = 0; i < kBloomMaxHashes; i++) pos[i] = i < k ? bloom_hash_mem(value, vs, seed + i) & mask : 0;
+  }
+#pragma unroll
+  for (uint32_t i = 0; i < kBloomMaxHashes; i++) {
+    const uint64_t a = m.data + 4ull * (pos[i] >> 5);
+    word[i] = i < k ? (coh ? acoh32(a) : ald32(a)) : ~0u;
+  }
+  bool all = true;
+#pragma unroll
+  for (uint32_t i = 0; i < kBloomMaxHashes; i++) {
+    const uint32_t bit = 1u << (pos[i] & 31);
+    if (PUSH) {
+      if (i < k && !(word[i] & bit))
+        __hip_atomic_fetch_or(G32(m.data + 4ull * (pos[i] >> 5)), bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+      all = all && (word[i] & bit);
+    }
+  }
+  return PUSH || all ? 0 : (uint64_t)-1;
+}
+
+// The Bloom filter helpers' one entry (interp.hip call_helper, which sends a
+// Bloom filter's helper-2 calls here too).  op: the helper id --
+//   87 bpf_map_push_elem(map, value, flags)  bloom_filter.cpp:337-362
+//   88 bpf_map_pop_elem(map, value)          :364-369 (nothing to pop)
+//   89 bpf_map_peek_elem(map, value)         :371-393
+//    2 bpf_map_update_elem on a Bloom filter :291-322 (a push, the key ignored)
+// 87 / 88 / 89 on any other map type: -ENOTSUP (map_handler.cpp:1378-1468;
+// there are no QUEUE / STACK maps here).
+__device__ __noinline__ uint64_t helper_bloom(const DMap *maps, uint64_t fd, uint64_t value, uint64_t flags,
+                                              uint32_t op, bool exact) {
+  if (fd >= kMaxFds) return (uint64_t)-1;
+  const DMap m = load_dmap(maps, fd);
+  if (m.type != MT_BLOOM_FILTER) return (uint64_t)(int64_t)-95;  // -ENOTSUP
+  if (op == 88 || !value) return (uint64_t)-1;                    // EOPNOTSUPP / EINVAL
+  if (op == 89) return bloom_probe<false>(m, value, exact);
+  if (flags != 0) return (uint64_t)-1;                            // BPF_ANY only
+  return bloom_probe<true>(m, value, exact);
+}
+
 __device__ uint64_t helper_lookup(const DMap *maps, uint64_t fd, uint64_t key, LaneEnv &env) {
   if (fd >= kMaxFds) return 0;
   const DMap m = load_dmap(maps, fd);

@@ -38,9 +38,22 @@
 namespace bpftime_amd {
 
 // Helper dispatch (helper id is wave-uniform); returns r0, sets *err.
+// BLOOM: the Bloom filter helpers are compiled in.  Only the scratch-stack
+// instances of k_interp and k_sys_seq carry them (the loader sends every
+// program that may reach a Bloom filter there, loader.cpp load_program): in
+// the LDS-stack instances the call to them cost the headline path 2 %
+// (Bloom filters).
+template <bool BLOOM>
 __device__ __forceinline__ uint64_t call_helper(uint32_t id, uint64_t a1, uint64_t a2, uint64_t a3, uint64_t a4,
                                                 uint64_t a5, const DMap *maps, uint32_t ncpu, uint64_t seed,
                                                 LaneEnv &env, uint32_t *err) {
+  if constexpr (BLOOM) {
+    // bpf_map_push / pop / peek_elem, and a Bloom filter's bpf_map_update_elem:
+    // a push of the value, the key ignored
+    const bool upd = id == 2 && a1 < kMaxFds && maps[a1].type == MT_BLOOM_FILTER;
+    if (id == 87 || id == 88 || id == 89 || upd)
+      return helper_bloom(maps, a1, upd ? a3 : a2, upd ? a4 : id == 87 ? a3 : 0, id, env.exact);
+  }
   switch (id) {
     case 1: return helper_lookup(maps, a1, a2, env);
     case 2: return helper_update(maps, a1, a2, a3, a4, env);
@@ -1104,7 +1117,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(4))) void k_
         env.ktime = p.kt_base ? *(const uint64_t *)(p.kt_base + unit * p.kt_stride) : 0;
         uint32_t cerr = E_OK;
         uint64_t *R = c.R;
-        const uint64_t rv = call_helper(c.call_id, R[1 * kBlock], R[2 * kBlock], R[3 * kBlock], R[4 * kBlock],
+        const uint64_t rv = call_helper<BIGSTACK>(c.call_id, R[1 * kBlock], R[2 * kBlock], R[3 * kBlock], R[4 * kBlock],
                                         R[5 * kBlock], p.maps, p.ncpu,
                                         (p.first_unit + unit) ^ ((uint64_t)c.steps << 40), env, &cerr);
         R[0] = rv;
@@ -1587,7 +1600,7 @@ __global__ __launch_bounds__(kBlock) void k_sys_seq(SeqParams p) {
           uint64_t *R = c.R;
           const uint32_t cid = __builtin_amdgcn_readfirstlane(c.call_id);
           const uint64_t rv = cid == kTailHelper ? 0
-                              : call_helper(cid, R[1 * kBlock], R[2 * kBlock], R[3 * kBlock], R[4 * kBlock],
+                              : call_helper<true>(cid, R[1 * kBlock], R[2 * kBlock], R[3 * kBlock], R[4 * kBlock],
                                             R[5 * kBlock], p.maps, p.ncpu, idx ^ ((uint64_t)c.steps << 40), env,
                                             &cerr);
           if (cid == kTailHelper) cerr = E_BADOP;  // (the host refuses such programs)

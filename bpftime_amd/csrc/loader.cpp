@@ -26,6 +26,7 @@ bool device_helper_supported(uint32_t id) {
     case 130: case 131: case 132: case 133:
     case 58: case 187:  // bpf_override_return / bpf_set_retval (syscall dispatch state)
     case 14:            // bpf_get_current_pid_tgid (recorded caller / launching thread)
+    case 87: case 88: case 89:  // bpf_map_push / pop / peek_elem (BLOOM_FILTER)
     case kTailHelper:
       return true;
   }
@@ -232,6 +233,8 @@ static int helper_arity(uint32_t id) {
   switch (id) {
     case 5: case 7: case 8: return 0;          // ktime_get_ns, get_prandom_u32, get_smp_processor_id
     case 1: case 3: case 44: case 65: return 2;  // map_lookup/delete_elem, xdp_adjust_head/tail
+    case 88: case 89: return 2;                // map_pop/peek_elem(map, value)
+    case 87: return 3;                         // map_push_elem(map, value, flags)
     case 2: case 189: return 4;                // map_update_elem, xdp_load_bytes
     case kTailHelper: return 3;                // tail_call(ctx, prog_array, index)
     case (uint32_t)kRetHelper: return 0;       // a linked tail-call target's exit
@@ -481,6 +484,7 @@ int load_program(const RawInsn *code, size_t n, const std::map<size_t, size_t> &
         return -EINVAL;
       }
       if (cur.imm == 3) out.may_delete = true;
+      if (cur.imm == 87 || cur.imm == 88 || cur.imm == 89) out.bloom = true;
       if (cur.imm == 58 || cur.imm == 187) out.sets_retval = true;
     } else if (cur.code == 0x18) {
       if (i + 1 == n) {
@@ -497,6 +501,10 @@ int load_program(const RawInsn *code, size_t n, const std::map<size_t, size_t> &
         case 1:
           if (!lddw.map_by_fd) { err = at + ", map_by_fd not defined"; return -EINVAL; }
           imm = lddw.map_by_fd((uint32_t)cur.imm);
+          {  // a Bloom filter named by fd: helper 2 on it is a push
+            Runtime &r = rt();
+            if (imm < kMaxFds && r.kind[imm] == HKind::MAP && r.maps[imm].type == MT_BLOOM_FILTER) out.bloom = true;
+          }
           break;
         case 2:
           if (!lddw.map_by_fd || !lddw.map_val) { err = at + ", map_by_fd or map_val not defined"; return -EINVAL; }
@@ -637,7 +645,9 @@ int load_program(const RawInsn *code, size_t n, const std::map<size_t, size_t> &
   int depth = entries.empty() ? stack_depth(p, reach) : -1;  // an image: every program on a 512-B stack
   out.multi_entry = !entries.empty();
   out.entries = entries;
-  if (depth < 0 || depth > (int)kLdsStackMax) {
+  // (a program that may reach a Bloom filter runs in the scratch-stack
+  // kernels: only they carry the Bloom helpers, interp.hip call_helper)
+  if (depth < 0 || depth > (int)kLdsStackMax || out.bloom) {
     out.big_stack = true;
     out.stack_size = kStackSize;
   } else {
@@ -1004,6 +1014,9 @@ static void accesses(const std::vector<DInsn> &p, uint32_t i, const std::vector<
     case 1: arg(2); return;
     case 2: arg(2); arg(3); map_values(); return;
     case 3: arg(2); map_values(); return;
+    case 87: arg(2); map_values(); return;  // push: reads the value, sets the map's bits
+    case 88: return;                        // pop: fails on every map type there is
+    case 89: arg(2); return;                // peek: reads the value (never written back)
     case 28: arg(1); arg(3); return;
     case 130: arg(2); return;
     case 132: case 133: arg(1); return;
@@ -1094,9 +1107,9 @@ static void const_loads(const std::vector<DInsn> &p, const std::vector<uint8_t> 
       case X_CALL:
         switch (d.hi) {
           case 1: case 5: case 7: case 8: case 14: case 28: case 58: case 187: case 130:
-          case 131: case 132: case 133: case 44: case 65:
-            break;  // no array-map writes (ring memory, the unit's ctx, dispatch state)
-          case 2: case 3:  // the values of the map in r1
+          case 131: case 132: case 133: case 44: case 65: case 88: case 89:
+            break;  // no array-map writes (ring memory, the unit's ctx, dispatch state; pop / peek write nothing)
+          case 2: case 3: case 87:  // the values of the map in r1
             if (st[1].kind == P_MAPFD) writes.push_back(Loc{Loc::MAPVAL, st[1].id, 0, kUnknownLen});
             else writes.push_back(Loc{Loc::ANY, -1, 0, 0});
             break;
@@ -1222,6 +1235,7 @@ static void tail_save_masks(const std::vector<DInsn> &p, const std::vector<std::
     if (d.op != X_CALL) continue;
     switch ((uint32_t)d.hi) {
       case 1: case 2: case 3: case 5: case 7: case 8: case 12: case 28: case 130: case 131: case 132: case 133:
+      case 87: case 88: case 89:  // push / pop / peek: no write to unit memory (peek leaves *value)
         break;
       case 44: case 65: ctx_bytes(0, 16); break;  // adjust_head / adjust_tail: data, data_end
       case 189: write(st[3], 0, 1 << 16); break;  // xdp_load_bytes(ctx, off, to, len)
@@ -1318,8 +1332,9 @@ static void map_effects(const std::vector<DInsn> &prog, const std::vector<std::v
         const PVal &m = st[1];
         const int32_t fd = m.kind == P_MAPFD ? m.id : -1;
         switch (d.hi) {
-          case 1: mark(fd, FX_READ); break;                             // map_lookup_elem
-          case 2: case 3: case 130: case 131: mark(fd, FX_WRITE); break;  // update, delete, ringbuf output / reserve
+          case 1: case 89: mark(fd, FX_READ); break;                    // map_lookup_elem, map_peek_elem
+          case 2: case 3: case 130: case 131: case 87: mark(fd, FX_WRITE); break;  // update, delete, ringbuf output / reserve, push
+          case 88:  // map_pop_elem: fails without touching the map
           case 5: case 7: case 8: case 14: case 28: case 44: case 58: case 65: case 132: case 133: case 187: case 189:
             break;  // no map effects (132 / 133 finish a reservation 131 marked)
           default: mark(-1, FX_READ | FX_WRITE); break;                 // bpf_tail_call, anything else

@@ -83,6 +83,7 @@ struct LoadOut {
   bool big_stack = false;    // 512-B scratch stack
   uint32_t fused_rmw = 0;
   uint32_t comb_entries = 0;  // per-block LDS combining entries (0 = none needed)
+  bool bloom = false;         // calls bpf_map_push / pop / peek_elem or names a BLOOM_FILTER: scratch-stack kernels only
   bool may_delete = false;    // calls map_delete_elem: hash lookup indexes stop being valid
   bool tail_call = false;     // calls bpf_tail_call: linked with the prog arrays' targets at launch
   bool sets_retval = false;   // calls bpf_override_return (58) / bpf_set_retval (187)

@@ -16,7 +16,9 @@
 #include <set>
 
 #include <algorithm>
+#include <chrono>
 #include <functional>
+#include <random>
 #include <vector>
 
 #include "../../include/bpftime_amd.h"
@@ -96,6 +98,16 @@ static MapRec *map_of(int fd) {
     return nullptr;
   }
   return &r.maps[fd];
+}
+
+// A Bloom filter's jhash seed: random per map, as the reference's is
+// (bloom_filter.cpp:91-92); the clock where the system has no entropy source
+static uint32_t bloom_random_seed() {
+  try {
+    return (uint32_t)std::random_device{}();
+  } catch (const std::exception &) {
+    return (uint32_t)std::chrono::steady_clock::now().time_since_epoch().count();
+  }
 }
 
 static int alloc_fd(int fd) {
@@ -1097,6 +1109,22 @@ int bpftime_maps_create(int fd, const char *name, struct bpf_map_attr attr) {
       m.bytes = 16 + (uint64_t)t->cap * d.slot_size;
       break;
     }
+    case MT_BLOOM_FILTER: {
+      // map_handler.cpp:860-884, bloom_filter.cpp:50-101: no key, nr_hashes
+      // in map_extra's low four bits (0: five), JHASH, a random seed per map
+      if (m.key_size != 0 || m.value_size == 0 || m.max_entries == 0) {
+        errno = EINVAL;
+        set_error("bloom filter needs key_size 0, value_size > 0, max_entries > 0");
+        return -1;
+      }
+      const uint32_t k = (uint32_t)(m.map_extra & 0xF) ? (uint32_t)(m.map_extra & 0xF) : 5;
+      const uint64_t bits = bloom_bits(m.max_entries, k);
+      d.nbuckets = (uint32_t)(bits - 1);  // common.hpp bloom_mask / bloom_hashes / bloom_seed
+      d.slot_size = k;
+      d.key_off = bloom_random_seed();
+      m.bytes = bits / 8;
+      break;
+    }
     default:
       errno = EINVAL;
       set_error("unsupported map type " + std::to_string(m.type));
@@ -1255,9 +1283,89 @@ static int prog_array_next_key(const MapRec &m, const void *key, void *next_key)
   return 0;
 }
 
+// ---- BLOOM_FILTER (runtime/src/bpf_map/userspace/bloom_filter.cpp) ----------
+// The bit array in the arena is the only copy: a host push or peek reads and
+// writes the bytes its probes name there, so it sees a finished batch's
+// pushes and the next batch sees its own.
+static long bloom_host_op(MapRec &m, const void *value, bool push) {
+  if (!value) {
+    errno = EINVAL;
+    return -1;
+  }
+  // the value as zero-padded little-endian words (common.hpp bloom_jhash_words)
+  std::vector<uint32_t> w((m.value_size + 11) / 12 * 3, 0);
+  memcpy(w.data(), value, m.value_size);
+  for (uint32_t i = 0; i < bloom_hashes(m.d); i++) {
+    const uint32_t bit = bloom_jhash_words(w.data(), m.value_size, bloom_seed(m.d) + i) & bloom_mask(m.d);
+    void *at = (void *)(m.d.data + bit / 8);
+    uint8_t b = 0;
+    if (hipMemcpy(&b, at, 1, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (b & (1u << (bit % 8))) continue;
+    if (!push) {
+      errno = ENOENT;
+      return -1;
+    }
+    b |= (uint8_t)(1u << (bit % 8));
+    if (hipMemcpy(at, &b, 1, hipMemcpyHostToDevice) != hipSuccess) return -1;
+  }
+  return 0;
+}
+
+// bpftime_shm.cpp:168-200 over map_handler.cpp:1378-1468: -ENOTSUP for a map
+// type without the operation (there are no QUEUE / STACK maps here)
+long bpftime_map_push_elem(int fd, const void *value, uint64_t flags) {
+  MapRec *m = map_of(fd);
+  if (!m) return -1;
+  if (m->type != MT_BLOOM_FILTER) return -ENOTSUP;
+  if (flags != 0) {  // bloom_filter.cpp:346-352: BPF_ANY only
+    errno = EINVAL;
+    return -1;
+  }
+  return bloom_host_op(*m, value, true);
+}
+
+long bpftime_map_peek_elem(int fd, void *value) {
+  MapRec *m = map_of(fd);
+  if (!m) return -1;
+  if (m->type != MT_BLOOM_FILTER) return -ENOTSUP;
+  return bloom_host_op(*m, value, false);
+}
+
+long bpftime_map_pop_elem(int fd, void *value) {
+  MapRec *m = map_of(fd);
+  (void)value;
+  if (!m) return -1;
+  if (m->type != MT_BLOOM_FILTER) return -ENOTSUP;
+  errno = EOPNOTSUPP;  // bloom_filter.cpp:364-369
+  return -1;
+}
+
+int bpftime_amd_bloom_seed(int fd, const uint32_t *set, uint32_t *out) {
+  Runtime &r = rt();
+  std::lock_guard<std::mutex> g(r.mu);
+  MapRec *m = map_of(fd);
+  if (!m || m->type != MT_BLOOM_FILTER) {
+    errno = EINVAL;
+    return -1;
+  }
+  if (set) {
+    // bits set under another seed mean nothing: the array starts over
+    // (batches still running finish first)
+    if (hipDeviceSynchronize() != hipSuccess || hipMemset((void *)m->d.data, 0, m->bytes) != hipSuccess) return -1;
+    m->d.key_off = *set;
+    if (r.push_map(fd) < 0) return -1;
+  }
+  if (out) *out = bloom_seed(m->d);
+  return 0;
+}
+
 const void *bpftime_map_lookup_elem(int fd, const void *key) {
   MapRec *m = map_of(fd);
   if (!m) return nullptr;
+  if (m->type == MT_BLOOM_FILTER) {  // bloom_filter.cpp:283-289: peek is the lookup
+    errno = EOPNOTSUPP;
+    return nullptr;
+  }
   if (m->type == MT_RINGBUF) {  // ringbuf_map.cpp: lookup / update / delete / next key unsupported
     errno = ENOTSUP;
     return nullptr;
@@ -1316,6 +1424,13 @@ long bpftime_map_update_elem(int fd, const void *key, const void *value, uint64_
   if (m->type == MT_RINGBUF) {
     errno = ENOTSUP;
     return -1;
+  }
+  if (m->type == MT_BLOOM_FILTER) {  // bloom_filter.cpp:291-322: a push, the key ignored
+    if (flags != 0) {
+      errno = EINVAL;
+      return -1;
+    }
+    return bloom_host_op(*m, value, true);
   }
   if (m->type == MT_PROG_ARRAY) return prog_array_update(*m, key, value);
   if (m->type == MT_LRU_HASH) return lru_host_update(*m, key, value, flags);
@@ -1421,6 +1536,10 @@ long bpftime_map_update_elem(int fd, const void *key, const void *value, uint64_
 long bpftime_map_delete_elem(int fd, const void *key) {
   MapRec *m = map_of(fd);
   if (!m) return -1;
+  if (m->type == MT_BLOOM_FILTER) {  // bloom_filter.cpp:324-335 (and next key below)
+    errno = EOPNOTSUPP;
+    return -1;
+  }
   if (m->type == MT_PROG_ARRAY) return prog_array_delete(*m, key);
   if (m->type == MT_LRU_HASH) return lru_host_delete(*m, key);
   if (m->type == MT_RINGBUF) {
@@ -1474,8 +1593,8 @@ long bpftime_map_delete_elem(int fd, const void *key) {
 int bpftime_map_get_next_key(int fd, const void *key, void *next_key) {
   MapRec *m = map_of(fd);
   if (!m) return -1;
-  if (m->type == MT_RINGBUF) {
-    errno = ENOTSUP;
+  if (m->type == MT_RINGBUF || m->type == MT_BLOOM_FILTER) {
+    errno = ENOTSUP;  // (= EOPNOTSUPP)
     return -1;
   }
   if (m->type == MT_LPM_TRIE) {

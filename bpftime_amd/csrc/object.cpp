@@ -479,7 +479,11 @@ struct bpftime_object {
             m.attr.key_size = (uint32_t)btf.size_of(pointee);
           } else if (mem.name == "value") {
             m.attr.value_size = (uint32_t)btf.size_of(pointee);
-          } else if (mem.name == "numa_node" || mem.name == "pinning" || mem.name == "map_extra") {
+          } else if (mem.name == "map_extra") {  // (a BLOOM_FILTER's nr_hashes)
+            uint32_t v = 0;
+            ok = uint_val(v);
+            m.attr.map_extra = v;
+          } else if (mem.name == "numa_node" || mem.name == "pinning") {
             uint32_t v = 0;
             ok = uint_val(v);
           } else {

@@ -36,6 +36,10 @@ extern "C" long bpftime_amd_handle_sysbpf(int cmd, void *attr_, uint32_t size) {
       a.btf_id = attr->btf_fd;
       a.btf_key_type_id = attr->btf_key_type_id;
       a.btf_value_type_id = attr->btf_value_type_id;
+      // map_extra follows btf_vmlinux_value_type_id in the kernel ABI (newer
+      // than this image's linux/bpf.h): read when the caller's attr has it
+      const size_t xoff = (offsetof(union bpf_attr, btf_vmlinux_value_type_id) + 4 + 7) & ~(size_t)7;
+      if (size >= xoff + 8) memcpy(&a.map_extra, (const uint8_t *)attr + xoff, 8);
       char name[BPF_OBJ_NAME_LEN + 1];
       memcpy(name, attr->map_name, BPF_OBJ_NAME_LEN);
       name[BPF_OBJ_NAME_LEN] = 0;

@@ -356,7 +356,7 @@ class Mi355xVm {
     if (img && img->gen == r.prog_gen && img->d_tail_entry) return 0;
     std::map<size_t, size_t> hm = helper_id_map;
     std::map<size_t, std::string> names = helper_names;
-    for (uint32_t id : {1u, 2u, 3u, 5u, 7u, 8u, 12u, 28u, 44u, 65u, 130u, 131u, 132u, 133u, 189u})
+    for (uint32_t id : {1u, 2u, 3u, 5u, 7u, 8u, 12u, 28u, 44u, 65u, 87u, 88u, 89u, 130u, 131u, 132u, 133u, 189u})
       if (!hm.count(id)) hm[id] = 63;  // the runtime's helper groups (bpf_helper.cpp:606-620)
     // prog arrays named by lddw src 1 in `code`
     auto arrays_of = [&](const RawInsn *code, size_t n, std::set<int32_t> &out) {
@@ -1444,7 +1444,8 @@ int bpftime_amd_register_default_helpers(struct ebpf_vm *vm) {
            {130, "bpf_ringbuf_output"},      {12, "bpf_tail_call"},
            {1, "bpf_map_lookup_elem"},       {2, "bpf_map_update_elem"}, {3, "bpf_map_delete_elem"},
            {58, "bpf_override_return"},      {187, "bpf_set_retval"},
-           {14, "bpf_get_current_pid_tgid"}};
+           {14, "bpf_get_current_pid_tgid"},
+           {87, "bpf_map_push_elem"},        {88, "bpf_map_pop_elem"},   {89, "bpf_map_peek_elem"}};
   int err = 0;
   for (auto &e : h) err |= ebpf_register(vm, e.id, e.name, nullptr);
   return err ? -1 : 0;

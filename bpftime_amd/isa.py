@@ -65,6 +65,9 @@ BPF_FUNC_set_retval = 187
 BPF_FUNC_csum_diff = 28
 BPF_FUNC_xdp_adjust_head = 44
 BPF_FUNC_xdp_adjust_tail = 65
+BPF_FUNC_map_push_elem = 87
+BPF_FUNC_map_pop_elem = 88
+BPF_FUNC_map_peek_elem = 89
 BPF_FUNC_ringbuf_output = 130
 BPF_FUNC_ringbuf_reserve = 131
 BPF_FUNC_ringbuf_submit = 132
@@ -80,6 +83,7 @@ BPF_MAP_TYPE_PERCPU_ARRAY = 6
 BPF_MAP_TYPE_LRU_HASH = 9
 BPF_MAP_TYPE_LPM_TRIE = 11
 BPF_MAP_TYPE_RINGBUF = 27
+BPF_MAP_TYPE_BLOOM_FILTER = 30
 BPF_ANY, BPF_NOEXIST, BPF_EXIST = 0, 1, 2
 BPF_F_MMAPABLE = 1 << 10
 

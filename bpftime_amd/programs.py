@@ -702,3 +702,54 @@ def tail_target_recurse(pa_fd: int, cnt_fd: int, slot: int) -> bytes:
     a.mov64(1, "r6").ld_map_fd(2, pa_fd).mov64(3, slot).call(_TAIL)
     a.add64(0, 1).exit()
     return a.assemble()
+
+
+# ---- BPF_MAP_TYPE_BLOOM_FILTER (bpf_map_push_elem / bpf_map_peek_elem) ------
+_PUSH, _PEEK = 87, 89
+
+
+def _ipv4_or_pass(a: Asm) -> None:
+    """r6 = data; frames shorter than Eth + IPv4 or of another ethertype
+    leave with XDP_PASS."""
+    a.ldx(8, 6, 1, 0)                     # r6 = data
+    a.ldx(8, 3, 1, 8)                     # r3 = data_end
+    a.mov64(4, "r6").add64(4, 34)
+    a.mov64(0, XDP_PASS)
+    a.jmp("jgt", 4, "r3", "out")          # short frame
+    a.ldx(2, 4, 6, 12)                    # h_proto
+    a.jmp("jne", 4, ETH_P_IP_LE, "out")   # not IPv4
+
+
+def bloom_blocklist(fd: int) -> bytes:
+    """Source-address blocklist: XDP_DROP when the IPv4 source address (4
+    bytes at packet offset 26, peeked in place) may be in the Bloom filter,
+    else XDP_PASS; non-IPv4 and short frames pass.  fd: BLOOM_FILTER, value 4."""
+    a = Asm()
+    _ipv4_or_pass(a)
+    a.ld_map_fd(1, fd)
+    a.mov64(2, "r6").add64(2, 26)         # r2 = &iph->saddr (2 mod 4: unaligned)
+    a.call(_PEEK)
+    a.mov64(1, "r0")
+    a.mov64(0, XDP_PASS)
+    a.jmp("jne", 1, 0, "out")             # -ENOENT: not in the filter
+    a.mov64(0, XDP_DROP)
+    a.label("out").exit()
+    return a.assemble()
+
+
+def bloom_first_seen(fd: int) -> bytes:
+    """Seen-before filter over the 8 bytes saddr||daddr at packet offset 26:
+    peek, then push, both with the value pointer aimed into the packet;
+    XDP_TX when the pair was (maybe) seen before, else XDP_PASS.
+    fd: BLOOM_FILTER, value 8."""
+    a = Asm()
+    _ipv4_or_pass(a)
+    a.add64(6, 26)                        # r6 = &iph->saddr
+    a.ld_map_fd(1, fd).mov64(2, "r6").call(_PEEK)
+    a.mov64(7, "r0")
+    a.ld_map_fd(1, fd).mov64(2, "r6").mov64(3, 0).call(_PUSH)
+    a.mov64(0, XDP_PASS)
+    a.jmp("jne", 7, 0, "out")
+    a.mov64(0, XDP_TX)
+    a.label("out").exit()
+    return a.assemble()

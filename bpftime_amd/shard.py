@@ -9,6 +9,7 @@ shards:
   * hash (additive)    key union, values merged by the same delta rule
   * per-CPU maps       virtual-CPU slots are global ((unit // 64) % ncpu),
                        so per-slot deltas add up the same way
+  * Bloom filters      bitwise OR of the shards' bit arrays (same seed)
 The array rule runs in libbpftime_amd (bpftime_amd_merge_delta).
 """
 from __future__ import annotations
@@ -75,6 +76,21 @@ def merge_hash_additive(init: Dict[bytes, bytes], shards: List[Dict[bytes, bytes
     if len(out) > max_entries:
         raise ValueError(f"merged hash map has {len(out)} keys > max_entries {max_entries}")
     return out
+
+
+def merge_bloom(shards: List[np.ndarray]) -> np.ndarray:
+    """A BLOOM_FILTER's shards (snapshots of filters made with one seed): a
+    push only sets bits, so the bitwise OR is the array one filter would hold
+    after every shard's pushes."""
+    if not shards:
+        raise ValueError("no shards")
+    acc = np.array(shards[0], dtype=np.uint8, copy=True).ravel()
+    for s in shards[1:]:
+        s = np.ascontiguousarray(s, dtype=np.uint8).ravel()
+        if s.nbytes != acc.nbytes:
+            raise ValueError("shard size mismatch")
+        acc |= s
+    return acc
 
 
 def u64(b: bytes, i: int = 0) -> int:

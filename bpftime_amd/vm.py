@@ -81,9 +81,9 @@ class DeviceBuffer:
 # ---------------------------------------------------------------------------
 class Map:
     def __init__(self, type_: int, key_size: int, value_size: int, max_entries: int, flags: int = 0,
-                 name: str = "", fd: int = -1):
+                 name: str = "", fd: int = -1, map_extra: int = 0):
         attr = BpfMapAttr(type=type_, key_size=key_size, value_size=value_size, max_ents=max_entries,
-                          flags=flags)
+                          flags=flags, map_extra=map_extra)
         self.fd = lib().bpftime_maps_create(fd, name.encode(), attr)
         if self.fd < 0:
             raise EbpfError(f"map create failed: {_err()}")
@@ -181,6 +181,29 @@ class Map:
 
     def count(self) -> int:
         return lib().bpftime_amd_map_count(self.fd)
+
+    # BPF_MAP_TYPE_BLOOM_FILTER (bpftime_shm.cpp:168-200)
+    def push(self, value: bytes, flags: int = 0) -> int:
+        v = C.create_string_buffer(bytes(value), len(value))
+        return lib().bpftime_map_push_elem(self.fd, v, flags)
+
+    def peek(self, value: bytes) -> bool:
+        """True when every bit of the value is set (it may have been pushed)."""
+        v = C.create_string_buffer(bytes(value), len(value))
+        return lib().bpftime_map_peek_elem(self.fd, v) == 0
+
+    def pop(self) -> int:
+        v = C.create_string_buffer(max(self.value_size, 1))
+        return lib().bpftime_map_pop_elem(self.fd, v)
+
+    def bloom_seed(self, set: Optional[int] = None) -> int:
+        """The filter's jhash seed; `set` installs a new one first, which
+        zeroes the bit array."""
+        out = C.c_uint32(0)
+        new = C.byref(C.c_uint32(set & 0xFFFFFFFF)) if set is not None else None
+        if lib().bpftime_amd_bloom_seed(self.fd, new, C.byref(out)) < 0:
+            raise EbpfError(f"fd {self.fd} is not a Bloom filter")
+        return out.value
 
     def close(self) -> None:
         lib().bpftime_close(self.fd)

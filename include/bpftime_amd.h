@@ -55,14 +55,25 @@ struct bpf_link_create_args {
 /* create a map at `fd` (-1: lowest unused fd).  Supported types: HASH (1,
  * fix-size hash, map_handler.cpp:54-58), ARRAY (2), PROG_ARRAY (3, prog
  * fds, prog_array.cpp; the targets of bpf_tail_call, linked into the caller's
- * image at launch), PERCPU_HASH (5), PERCPU_ARRAY (6), LPM_TRIE (11),
- * RINGBUF (27).  Returns fd or -1 (errno set). */
+ * image at launch), PERCPU_HASH (5), PERCPU_ARRAY (6), LRU_HASH (9),
+ * LPM_TRIE (11), RINGBUF (27), BLOOM_FILTER (30: key_size 0, nr_hashes =
+ * map_extra & 0xF with 0 meaning 5, bloom_filter.cpp).  Returns fd or -1
+ * (errno set). */
 int bpftime_maps_create(int fd, const char *name, struct bpf_map_attr attr);
 /* syscall-side ops (from_syscall = true), bpftime_shm.cpp:115-140 */
 const void *bpftime_map_lookup_elem(int fd, const void *key);
 long bpftime_map_update_elem(int fd, const void *key, const void *value, uint64_t flags);
 long bpftime_map_delete_elem(int fd, const void *key);
 int bpftime_map_get_next_key(int fd, const void *key, void *next_key);
+/* bpftime_shm.cpp:168-200.  A BLOOM_FILTER takes push (flags must be 0: sets
+ * the value's bits, returns 0) and peek (0 when every bit of the value is
+ * set, else -1 with ENOENT; *value is not written); pop gives -1 with
+ * EOPNOTSUPP.  Every other map type: -ENOTSUP.  lookup / delete /
+ * get_next_key on a BLOOM_FILTER fail with EOPNOTSUPP, update is a push (the
+ * key, which may be NULL, is ignored). */
+long bpftime_map_push_elem(int fd, const void *value, uint64_t flags);
+long bpftime_map_pop_elem(int fd, void *value);
+long bpftime_map_peek_elem(int fd, void *value);
 uint32_t bpftime_map_value_size_from_syscall(int fd);
 int bpftime_is_map_fd(int fd);
 int bpftime_is_array_map(int fd);
@@ -174,6 +185,11 @@ int bpftime_amd_map_restore(int fd, const void *in, uint64_t bytes);
 int bpftime_amd_map_geometry(int fd, uint64_t *nbuckets, uint32_t *slot_size, uint32_t *key_off,
                              uint32_t *val_off, uint32_t *ncpu);
 uint64_t bpftime_amd_map_count(int fd);
+/* BLOOM_FILTER: the jhash seed (drawn at random per map, as the reference
+ * draws it) to *out; a non-NULL `set` installs *set first and zeroes the bit
+ * array -- bits set under another seed mean nothing.  0, or -1 (not a Bloom
+ * filter). */
+int bpftime_amd_bloom_seed(int fd, const uint32_t *set, uint32_t *out);
 /* An LPM trie whose device update (ORDERED batch) ran out of the node pool
  * keeps the state from before that batch and reports ENOMEM on every host op
  * and every launch of a program naming a trie until this acknowledges it:
