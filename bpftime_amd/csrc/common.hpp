@@ -207,7 +207,7 @@ constexpr uint32_t kIxProbes = 8;  // asm tier: index probes before the C++ tier
 // An index entry an insert holds while it claims a bucket for its key
 // (dev_helpers.hpp hash_find_ix), and the table's bucket bitmap after the
 // index: bit b = bucket b is not EMPTY (bits past nbuckets set), kept by
-// device inserts while the index is valid and rebuilt with it (maps.cpp)
+// device inserts while the index is valid and rebuilt with it (map_hash.cpp)
 constexpr uint32_t kIxRes = 0xffffffffu;
 // Keyed indexes (keys of at most 16 B): beside the u32 entries, the key of
 // each entry at the same position in an array of 8-B (keys <= 8 B) or 16-B
@@ -287,10 +287,10 @@ constexpr uint32_t CTX_SYSCALL = 2;  // r1 = trace_event_raw_sys_enter (64 B) or
                                      // EBPF_CTX_SYSCALL_EXIT batches, trace_event_raw_sys_exit (24 B)
 
 // Launches of at least this many units build the flat table of an IPv4 LPM
-// trie changed since the last one (maps.cpp prepare_ix); smaller ones walk
+// trie changed since the last one (map_lpm.cpp lpm_prepare_launch); smaller ones walk
 constexpr uint64_t kLpmFlatMinUnits = 1ull << 16;
 // LPM replica header word 3: an ORDERED batch's update found the node pool
-// full (dev_helpers.hpp lpm_update; the host fails the batch, maps.cpp)
+// full (dev_helpers.hpp lpm_update; the host fails the batch, map_lpm.cpp)
 constexpr uint32_t kLpmPoolOut = 0x80000000u;
 
 // Ring-buffer staging per block (dev_helpers.hpp RbStage)

@@ -257,7 +257,7 @@ __device__ uint64_t ix_insert(const DMap &m, uint64_t key, uint64_t h, uint64_t 
 }
 
 // hash_find over a valid lookup index: the index holds exactly the keys the
-// reference probe reaches (maps.cpp ix_rebuild; device inserts index what
+// reference probe reaches (map_hash.cpp ix_rebuild; device inserts index what
 // they publish), so walking it from ix_pos(h) to an empty entry decides
 // presence without the reference probe's walk of a nearly full table (config
 // 3: 65,536 flows in 65,537 buckets).  An empty entry is confirmed at the
@@ -343,7 +343,7 @@ __device__ uint64_t hash_find(const DMap &m, uint64_t key, bool insert, uint64_t
   uint32_t spins = 0;
   for (;;) {
     uint64_t s = m.data + idx * (uint64_t)m.slot_size;
-    // A slot never straddles a 128-B line (maps.cpp slot sizing), so a
+    // A slot never straddles a 128-B line (map_hash.cpp hash_geometry), so a
     // FILLED state read by a load comes with the key bytes of that same
     // line snapshot.  Anything else is confirmed at the coherence point: a
     // stale EMPTY from this XCD's L2 would end the probe with a false miss.
@@ -597,7 +597,7 @@ __device__ uint64_t lpm_lookup(const DMap &m, uint64_t key) {
   if (kp > maxp) return 0;
   const uint8_t *kd = (const uint8_t *)(uintptr_t)(key + 4);
   if (m.ix && kp == 32 && dsz == 4) {
-    // IPv4 full-length key: the flat table (maps.cpp LpmTrie::flat)
+    // IPv4 full-length key: the flat table (lpm_trie.hpp LpmTrie::flat)
     const uint32_t *t = (const uint32_t *)(uintptr_t)m.ix;
     uint32_t e = t[((uint32_t)kd[0] << 16) | ((uint32_t)kd[1] << 8) | kd[2]];
     if (e & 0x80000000u) e = t[(1u << 24) + 256u * (e & 0x7fffffffu) + kd[3]];
@@ -630,10 +630,10 @@ __device__ uint64_t lpm_lookup(const DMap &m, uint64_t key) {
 // units in order; vm_api.cpp refuses other batches of such programs):
 // lpm_trie_map.cpp:266-488 (elem_update) and :490-541 (elem_delete, a
 // logical deletion: the node becomes intermediate) restated over the
-// replica exactly as the host's LpmTrie::update / remove (maps.cpp) do over
+// replica exactly as the host's LpmTrie::update / remove (lpm_trie.hpp) do over
 // its node pool -- new nodes appended at index `nodes`, the same numbering,
 // so the host takes the replica back as its trie after the batch
-// (maps.cpp lpm_pull).  Replica header {i32 root, u32 nodes, u32 entries,
+// (map_lpm.cpp lpm_pull).  Replica header {i32 root, u32 nodes, u32 entries,
 // u32 cap}; a node {u32 plen, u32 intermediate, i32 child[2], data at
 // key_off, value at val_off}.  Errors return -1 like the reference helper.
 struct LpmHdr {
@@ -665,9 +665,9 @@ __device__ uint64_t lpm_update(const DMap &m, uint64_t key, uint64_t val, uint64
   auto need_room = [&]() {
     if (flags == 2) return false;                    // ENOENT
     if (h->entries >= m.max_entries) return false;   // ENOSPC
-    // the replica's node pool (maps.cpp): running out of it is no answer
+    // the replica's node pool (map_lpm.cpp): running out of it is no answer
     // the reference gives (its heap grows), so it is flagged in the
-    // header and the host fails the batch (maps.cpp lpm_pull)
+    // header and the host fails the batch (map_lpm.cpp lpm_pull)
     if (h->nodes + 2 <= (h->cap & ~kLpmPoolOut)) return true;
     h->cap |= kLpmPoolOut;
     return false;
@@ -1312,7 +1312,7 @@ __device__ uint64_t helper_lookup(const DMap *maps, uint64_t fd, uint64_t key, L
       const int32_t v = *(const volatile int32_t *)(m.data + 4ull * (uint32_t)k);
       if (v < 0) return 0;
       // the copy: this lane's scratch word when the launch has them (the
-      // reference's thread-local), else the array's shadow half (maps.cpp);
+      // reference's thread-local), else the array's shadow half (maps.cpp bpftime_maps_create);
       // either way a write through the pointer never reaches the array
       const uint64_t c = env.scratch ? env.scratch : m.data + 4ull * m.max_entries + 4ull * (uint32_t)k;
       *(volatile int32_t *)c = v;

@@ -1157,7 +1157,7 @@ class Gen:
 
     def lpm_lookup(self):
         """LPM_TRIE with a 4-byte (IPv4) key on the stack whose prefixlen is
-        32 in every lane: the flat table (maps.cpp LpmTrie::flat, DMap.ix):
+        32 in every lane: the flat table (lpm_trie.hpp LpmTrie::flat, DMap.ix):
         e = t[top 24 address bits], e = group[e][low byte] when bit 31 is
         set; r0 = e ? &value of node e - 1 in the replica : 0 -- the node the
         trie walk (dev_helpers.hpp lpm_lookup) returns.  Other keys, and
@@ -1238,7 +1238,7 @@ class Gen:
     # the entry; a reader reads the entries before the keys, and one CU's LDS
     # keeps every wave's accesses in order, so an entry it sees is complete.
     # Only hash lookups the loader marked FW_LCACHE use it: nothing deletes
-    # during their launch (the program cannot, and vm_api.cpp / maps.cpp keep
+    # during their launch (the program cannot, and vm_api.cpp / map_hash.cpp keep
     # every other deleting launch and host delete from overlapping it), so a
     # slot found for a key stays that key's slot.  A probe leaves v82 / v83 =
     # the key / entry address of the set's first empty way (v83 = -1: none)

@@ -27,7 +27,11 @@ struct MapRec {
   uint64_t bytes = 0;  // storage bytes at d.data
   uint64_t ix_addr = 0;    // hash lookup index storage (common.hpp ix_pos), 0 = none
   bool ix_valid = false;   // d.ix = ix_addr while the index holds exactly the reachable keys
-  std::shared_ptr<struct LpmTrie> lpm;  // LPM_TRIE: the authoritative host trie
+  std::shared_ptr<struct LpmTrie> lpm;  // LPM_TRIE: the authoritative host trie (lpm_trie.hpp)
+  // LPM_TRIE: the device flat table of a 4-byte-key trie (LpmTrie::flat;
+  // DMap.ix), 0 = none; freed when the map goes (map_lpm.cpp lpm_drop_flat)
+  void *lpm_flat = nullptr;
+  uint64_t lpm_flat_bytes = 0;
   // LPM_TRIE: an ORDERED batch's device update ran out of the node pool;
   // every host op on the trie and every launch naming a trie reports it
   // (ENOMEM) until bpftime_amd_map_ack_error
@@ -38,7 +42,7 @@ struct MapRec {
   uint32_t kernel_bpf_map_id = 0;
   // host view of an ARRAY map (bpftime_get_array_map_raw_data, the mmap a
   // libbpf loader makes of .bss / .data): page-aligned host bytes kept
-  // coherent with the device copy at batch boundaries (maps.cpp host_view_*)
+  // coherent with the device copy at batch boundaries (map_array.cpp)
   uint8_t *host_view = nullptr;
   uint64_t host_view_bytes = 0;
   std::vector<uint8_t> host_shadow;  // the bytes last exchanged with the device
@@ -70,7 +74,7 @@ struct ProgRec {
 
 struct LinkRec {
   uint32_t prog_fd = 0, target = 0, attach_type = 0, flags = 0;
-  bool perf = false;  // target is a perf event record (maps.cpp link_perf)
+  bool perf = false;  // target is a perf event record (handles.cpp link_perf)
   int attach_id = 0;  // a perf link to a sys_enter / sys_exit tracepoint: its syscall attachment (syscall_dispatch.cpp)
 };
 
@@ -104,7 +108,7 @@ struct Runtime {
   std::set<int> lpm_flat_pending;  // IPv4 LPM tries whose flat table is not built (DMap.ix = 0: walk)
   // LPM tries an ORDERED batch of a program that writes them may have
   // changed on the device: the replica is authoritative until the host pulls
-  // it back (maps.cpp lpm_pull) before its next operation on the trie
+  // it back (map_lpm.cpp lpm_pull) before its next operation on the trie
   std::set<int> lpm_dev_dirty;
   // before a launch: a program that can delete invalidates every hash
   // lookup index; any other rebuilds the stale ones.  `lpm_written`: the LPM
@@ -119,7 +123,7 @@ struct Runtime {
   // lookup cache (a found slot is trusted for the rest of the launch), one of
   // a program that can delete.  A cached launch never overlaps a deletion
   // (a program's, on any stream, or the host's): whichever comes second
-  // waits for the device first (vm_api.cpp exec_batch, maps.cpp host delete)
+  // waits for the device first (vm_api.cpp exec_batch, map_hash.cpp hash_erase)
   std::atomic<bool> lcache_inflight{false}, deleter_inflight{false};
   // LPM tries (vm_api.cpp exec_batch): launches of a runtime holding any are
   // prepared and launched under lpm_launch_mu; a launch that may write a
@@ -137,7 +141,7 @@ struct Runtime {
   uint64_t prepare_lru();
 };
 
-// hash lookup index upkeep for host-side writes (maps.cpp)
+// hash lookup index upkeep for host-side writes (map_hash.cpp)
 void ix_invalidate(int fd);
 // the device replica of an LPM trie an ORDERED batch wrote, back into the
 // host trie (no-op unless the trie is in lpm_dev_dirty)
@@ -145,6 +149,9 @@ int lpm_pull(int fd);
 
 Runtime &rt();
 void set_error(const std::string &e);
+// `fd` when it is free, the lowest free fd for -1; else -1 and EBADF
+// (runtime.cpp; the caller holds the runtime lock)
+__attribute__((visibility("hidden"))) int alloc_fd(int fd);
 
 // What the syscall dispatch needs to know of a loaded VM's program
 // (vm_api.cpp): bit 0 it calls bpf_override_return / bpf_set_retval (58 /

@@ -1079,7 +1079,7 @@ int Mi355xVm::exec_batch(const ebpf_batch *b) {
       return -1;
     }
     // a program-side LPM update that ran out of the device node pool fails
-    // the batch here (maps.cpp lpm_pull; asynchronous batches report it at
+    // the batch here (map_lpm.cpp lpm_pull; asynchronous batches report it at
     // the trie's next use)
     for (const int fd : lpm_w) {
       std::lock_guard<std::mutex> g(r.mu);

@@ -1,16 +1,12 @@
-// The LPM flat table (maps.cpp LpmTrie::flat) against the trie walk
+// The LPM flat table (lpm_trie.hpp LpmTrie::flat) against the trie walk
 // (LpmTrie::lookup, the restatement of lpm_trie_map.cpp:192-264) on random
 // IPv4 route sets with updates and logical deletions, every /32 of sampled
 // /24s and random addresses.  Host-only: built by tests/test_lpm_flat.py.
-#include "../../bpftime_amd/csrc/maps.cpp"
+#include "../../bpftime_amd/csrc/lpm_trie.hpp"
+
+#include <stdio.h>
 
 #include <random>
-
-// maps.cpp's only references outside itself (the perf-event attach path)
-extern "C" int bpftime_amd_syscall_attach_ex(int, int64_t, int) { return -1; }
-extern "C" int bpftime_amd_syscall_detach(int) { return -1; }
-extern "C" int bpftime_amd_tracepoint_resolve(int32_t, int64_t *, int *) { return -1; }
-void bpftime_amd::syscall_detach_all() {}
 
 using bpftime_amd::LpmTrie;
 

@@ -1,5 +1,5 @@
 """BPF_MAP_TYPE_LRU_HASH on the device (common.hpp LRU_HASH, dev_helpers.hpp
-lru_*, maps.cpp lru_host_*) against the oracle's restatement of
+lru_*, map_lru.cpp lru_host_*) against the oracle's restatement of
 lru_var_hash_map.cpp:
   * the reference's own LRU unit tests over the host-side (syscall) ops;
   * a random op script: identical results / errno / values on both;

@@ -1,4 +1,4 @@
-"""The device LPM flat table (maps.cpp LpmTrie::flat, the DIR-24-8 form of
+"""The device LPM flat table (lpm_trie.hpp LpmTrie::flat, the DIR-24-8 form of
 an IPv4 trie that device lookups of full-length keys take) against the trie
 walk it replaces (LpmTrie::lookup, lpm_trie_map.cpp:192-264), host-only:
 random route sets with stray bits beyond the prefix, logical deletions
