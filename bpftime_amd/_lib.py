@@ -108,6 +108,7 @@ SIGNATURES = [
     ("bpftime_amd_set_step_limit", None, [C.c_void_p, C.c_uint64]),
     ("bpftime_amd_last_batch_ms", C.c_float, [C.c_void_p]),
     ("bpftime_amd_vm_fast_info", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("bpftime_amd_vm_fast_handler", C.c_char_p, [C.c_void_p, C.c_uint32, C.c_uint32]),
     ("bpftime_amd_vm_counter_info", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32),
                                               C.POINTER(C.c_uint32)]),
     ("bpftime_import_global_shm_from_json", C.c_int, [C.c_char_p]),

@@ -353,7 +353,28 @@ __device__ __forceinline__ uint32_t run_loop(Ctx &c) {
         const uint64_t a = RG(d.dst) + (int64_t)d.off;
         const uint64_t v = RG(d.src);
         const bool ok = c.win.ok(a, w64 ? 8 : 4);
-        const uint64_t ea = sel && ok ? a : c.dummy;
+        // The unit's own stack (LDS, or scratch: a flat address there names
+        // another location in every lane, and flat atomics are not defined
+        // on the private aperture): no other writer, so a plain load /
+        // compute / store as in X_RMW_ADD.  Those lanes' atomics go to the
+        // dummy slot; lold is what they fetched.
+        const bool loc = sel && ok && (is_lds_addr(a) || is_scratch_addr(a));
+        const uint64_t ea = sel && ok && !loc ? a : c.dummy;
+        uint64_t lold = 0;
+        if (loc) {
+          const uint32_t sz = w64 ? 8 : 4;
+          const uint64_t m = w64 ? ~0ull : 0xffffffffull;
+          const uint32_t aop = (uint32_t)d.hi & ~1u;
+          lold = mem_load(a, sz);
+          uint64_t nv;
+          if (d.hi == 0xf1) nv = lold == (RG(0) & m) ? v : lold;
+          else if (d.hi == 0xe1) nv = v;
+          else if (aop == 0x00) nv = lold + v;
+          else if (aop == 0x40) nv = lold | v;
+          else if (aop == 0x50) nv = lold & v;
+          else nv = lold ^ v;
+          mem_store(a, sz, nv);
+        }
         if (d.hi == 0xf1) {  // CMPXCHG: r0 = old
           const uint64_t r0 = RG(0);
           uint64_t res;
@@ -368,18 +389,18 @@ __device__ __forceinline__ uint32_t run_loop(Ctx &c) {
                                                  __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             res = e;
           }
-          WRO(0, res, r0);
+          WRO(0, loc ? lold : res, r0);
         } else if (d.hi == 0xe1) {  // XCHG
           const uint64_t old = w64 ? __hip_atomic_exchange((uint64_t *)ea, v, __ATOMIC_RELAXED,
                                                            __HIP_MEMORY_SCOPE_AGENT)
                                    : (uint64_t)__hip_atomic_exchange((uint32_t *)ea, (uint32_t)v, __ATOMIC_RELAXED,
                                                                      __HIP_MEMORY_SCOPE_AGENT);
-          WRO(d.src, old, v);
+          WRO(d.src, loc ? lold : old, v);
         } else if (d.hi == 0x00) {
           // add without fetch: lanes adding to one address are summed across
           // the wave and one of them adds (same-address device atomics
           // serialize at the memory side); the final value is the same
-          uint64_t pend = __ballot(sel && ok);
+          uint64_t pend = __ballot(sel && ok && !loc);
           while (pend) {
             const int leader = __builtin_ctzll(pend);
             const uint64_t la = readlane64(a, leader);
@@ -411,7 +432,7 @@ __device__ __forceinline__ uint32_t run_loop(Ctx &c) {
             else if (aop == 0x50) old = __hip_atomic_fetch_and(q, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             else old = __hip_atomic_fetch_xor(q, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           }
-          if (d.hi & 1) WRO(d.src, old, v);
+          if (d.hi & 1) WRO(d.src, loc ? lold : old, v);
         }
         if (__ballot(sel && !ok) != 0) {
           c.err = (sel && !ok) ? E_OOB : c.err;

@@ -1488,6 +1488,14 @@ int bpftime_amd_vm_fast_info(const struct ebpf_vm *vm, uint32_t ctx_kind, uint32
   return 0;
 }
 
+const char *bpftime_amd_vm_fast_handler(const struct ebpf_vm *vm, uint32_t ctx_kind, uint32_t pc) {
+  if (!vm || !vm->impl->loaded) return nullptr;
+  auto im = vm->impl->image();
+  const FastForm &f = ctx_kind == CTX_XDP ? im->fx : im->fr;
+  if (pc >= f.fast.size() || f.fast[pc].hoff < 4) return nullptr;
+  return fop_name((f.fast[pc].hoff - 4) / 4);
+}
+
 int bpftime_amd_vm_counter_info(const struct ebpf_vm *vm, uint32_t ctx_kind, uint32_t *deferred, uint32_t *direct) {
   if (!vm || !vm->impl->loaded) return -1;
   auto im = vm->impl->image();

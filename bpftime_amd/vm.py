@@ -282,6 +282,12 @@ class VM:
             raise EbpfError("vm_fast_info failed")
         return n.value
 
+    def fast_handler(self, kind: int, pc: int) -> Optional[str]:
+        """Name of the fast-path handler chosen for instruction slot `pc`
+        ("SLOW": left to the C++ tier); None past the program."""
+        s = lib().bpftime_amd_vm_fast_handler(C.c_void_p(self.h), kind, pc)
+        return s.decode() if s else None
+
     def counter_info(self, kind: int) -> tuple:
         """(deferred, direct) counter-add sites for the entry form of `kind`."""
         d, n = C.c_uint32(), C.c_uint32()

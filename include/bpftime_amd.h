@@ -217,6 +217,10 @@ float bpftime_amd_last_batch_ms(struct ebpf_vm *vm);
 /* loads/stores (and array-lookup keys) the loader typed statically for the
  * fast path under the given ctx kind (packet, slot, ctx or stack bases) */
 int bpftime_amd_vm_fast_info(const struct ebpf_vm *vm, uint32_t ctx_kind, uint32_t *specialized);
+/* The fast path's handler for instruction slot `pc` under the given ctx kind,
+ * by name ("SLOW": the C++ tier runs it); NULL when nothing is loaded or pc
+ * is past the program. */
+const char *bpftime_amd_vm_fast_handler(const struct ebpf_vm *vm, uint32_t ctx_kind, uint32_t pc);
 /* Counter adds of the loaded program for one entry form: `deferred` may be
  * summed per wave / block before they reach memory (nothing the unit runs
  * afterwards can observe them), `direct` reach memory at once. */

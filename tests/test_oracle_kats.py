@@ -152,6 +152,53 @@ def test_atomics(fresh_oracle):
     assert run(p.assemble()) == 255 + (10 << 8) + (15 << 16) + (7 << 32)
 
 
+def spec_atomic(imm, w32, old, v, r0):
+    """BPF_ATOMIC (kernel Documentation/bpf/standardization, atomic
+    operations) restated: (memory, source register, r0) afterwards.  32-bit
+    forms work on truncated operands and zero-extend what they fetch."""
+    m = M32 if w32 else M64
+    old, v = old & m, v & m
+    if imm == isa.ATOMIC_CMPXCHG:
+        return (v if old == r0 & m else old), None, old
+    if imm == isa.ATOMIC_XCHG:
+        return v, old, r0
+    new = {isa.ATOMIC_ADD: old + v, isa.ATOMIC_OR: old | v, isa.ATOMIC_AND: old & v,
+           isa.ATOMIC_XOR: old ^ v}[imm & ~isa.ATOMIC_FETCH] & m
+    return new, (old if imm & isa.ATOMIC_FETCH else None), r0
+
+
+ATOMIC_FORMS = [(f"{name}{'_fetch' if f else ''}", imm | f)
+                for name, imm in [("add", isa.ATOMIC_ADD), ("or", isa.ATOMIC_OR), ("and", isa.ATOMIC_AND),
+                                  ("xor", isa.ATOMIC_XOR)] for f in (0, isa.ATOMIC_FETCH)]
+ATOMIC_FORMS += [("xchg", isa.ATOMIC_XCHG), ("cmpxchg", isa.ATOMIC_CMPXCHG)]
+
+
+@pytest.mark.parametrize("w32", [False, True])
+@pytest.mark.parametrize("name,imm", ATOMIC_FORMS)
+def test_atomic_forms(fresh_oracle, name, imm, w32):
+    """All 20 forms on the stack: memory (the 4 bytes after a 32-bit target
+    included), the source register and r0 afterwards."""
+    from oracle import pyoracle as po
+    for cell in VALUES:
+        for v in VALUES[::3]:
+            old = cell & (M32 if w32 else M64)
+            # r0: equal, equal in the low word only, different
+            for r0 in ([old, old ^ (0xABCD << 32), old ^ 1] if imm == isa.ATOMIC_CMPXCHG else [0x5A5A5A5A5A5A5A5A]):
+                p = Asm().mov64(6, "r1").lddw(1, cell).stx(8, 10, -8, "r1").lddw(2, v).lddw(0, r0)
+                p.atomic(4 if w32 else 8, imm, 10, -8, "r2").ldx(8, 3, 10, -8)
+                p.stx(8, 6, 0, "r3").stx(8, 6, 8, "r2").stx(8, 6, 16, "r0").exit()
+                vm = po.OracleVM()
+                vm.load(p.assemble())
+                out = bytearray(24)
+                assert vm.exec(out)[0] == 0
+                mem, src, ret = struct.unpack("<3Q", out)
+                want_mem, want_src, want_r0 = spec_atomic(imm, w32, cell, v, r0)
+                if w32:
+                    want_mem |= cell & ~M32
+                assert (mem, src, ret) == (want_mem, v if want_src is None else want_src, want_r0), \
+                    (name, hex(cell), hex(v), hex(r0))
+
+
 def test_kat_bpf_progs_h(fresh_oracle):
     # vm/example/bpf_progs.h:6-11 / :44-57: d->a + d->b
     mem = struct.pack("<II", 40, 2)
