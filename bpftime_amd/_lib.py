@@ -81,6 +81,7 @@ SIGNATURES = [
     ("bpftime_map_push_elem", C.c_long, [C.c_int, C.c_void_p, C.c_uint64]),
     ("bpftime_map_pop_elem", C.c_long, [C.c_int, C.c_void_p]),
     ("bpftime_map_peek_elem", C.c_long, [C.c_int, C.c_void_p]),
+    ("bpftime_amd_map_type_supported", C.c_int, [C.c_uint32]),
     ("bpftime_amd_bloom_seed", C.c_int, [C.c_int, u32p, u32p]),
     ("bpftime_map_value_size_from_syscall", C.c_uint32, [C.c_int]),
     ("bpftime_is_map_fd", C.c_int, [C.c_int]),

@@ -85,6 +85,8 @@ constexpr uint32_t MT_PERCPU_HASH = 5;
 constexpr uint32_t MT_PERCPU_ARRAY = 6;
 constexpr uint32_t MT_LRU_HASH = 9;
 constexpr uint32_t MT_LPM_TRIE = 11;
+constexpr uint32_t MT_QUEUE = 22;
+constexpr uint32_t MT_STACK = 23;
 constexpr uint32_t MT_RINGBUF = 27;
 constexpr uint32_t MT_BLOOM_FILTER = 30;
 
@@ -117,6 +119,11 @@ constexpr uint32_t MT_BLOOM_FILTER = 30;
 //                  nbuckets = mask (bits - 1, a power of two minus one),
 //                  slot_size = nr_hashes (1..15), key_off = the jhash seed
 //                  (bloom_mask / bloom_hashes / bloom_seed below)
+//   QUEUE / STACK  one ring for both: a 128-B header line at data {u64 head,
+//                  u64 tail}, then max_entries slots; slot_size = the slot
+//                  stride (value_size rounded up to 4), val_off = 128 (slot 0's
+//                  offset from data); the element with ticket t lives in slot
+//                  t % max_entries, count = tail - head (qs_* below)
 struct DMap {
   uint32_t type;
   uint32_t key_size;
@@ -133,6 +140,19 @@ struct DMap {
   uint64_t ix;          // device address of the u32 lookup index, 0 = not valid (LPM_TRIE: its flat table)
 };
 static_assert(sizeof(DMap) == 64, "DMap must be 64 bytes");
+
+// QUEUE / STACK (runtime/src/bpf_map/userspace/queue.cpp, stack.cpp).  Push
+// writes the slot of ticket `tail`; a queue pops at `head`, a stack at `tail -
+// 1`; BPF_EXIST on a full ring advances `head` (the queue's head, the stack's
+// bottom).  The DMap fields the ring reuses:
+constexpr uint32_t kQsHeader = 128;  // the header line: u64 head at 0, u64 tail at 8
+inline BA_HD bool qs_type(uint32_t type) { return type == MT_QUEUE || type == MT_STACK; }
+inline BA_HD uint32_t qs_stride(const DMap &m) { return m.slot_size; }
+inline BA_HD uint64_t qs_head_addr(const DMap &m) { return m.data; }
+inline BA_HD uint64_t qs_tail_addr(const DMap &m) { return m.data + 8; }
+inline BA_HD uint64_t qs_slot(const DMap &m, uint64_t ticket) {
+  return m.data + m.val_off + (ticket % m.max_entries) * m.slot_size;
+}
 
 // BLOOM_FILTER (runtime/src/bpf_map/userspace/bloom_filter.cpp).  The DMap
 // fields a Bloom filter reuses:

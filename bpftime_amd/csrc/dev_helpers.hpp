@@ -1256,8 +1256,8 @@ __device__ __forceinline__ uint64_t bloom_probe(const DMap &m, uint64_t value, b
 //   88 bpf_map_pop_elem(map, value)          :364-369 (nothing to pop)
 //   89 bpf_map_peek_elem(map, value)         :371-393
 //    2 bpf_map_update_elem on a Bloom filter :291-322 (a push, the key ignored)
-// 87 / 88 / 89 on any other map type: -ENOTSUP (map_handler.cpp:1378-1468;
-// there are no QUEUE / STACK maps here).
+// 87 / 88 / 89 on any other map type but QUEUE / STACK (helper_qs below):
+// -ENOTSUP (map_handler.cpp:1378-1468).
 __device__ __noinline__ uint64_t helper_bloom(const DMap *maps, uint64_t fd, uint64_t value, uint64_t flags,
                                               uint32_t op, bool exact) {
   if (fd >= kMaxFds) return (uint64_t)-1;
@@ -1267,6 +1267,152 @@ __device__ __noinline__ uint64_t helper_bloom(const DMap *maps, uint64_t fd, uin
   if (op == 89) return bloom_probe<false>(m, value, exact);
   if (flags != 0) return (uint64_t)-1;                            // BPF_ANY only
   return bloom_probe<true>(m, value, exact);
+}
+
+// ---------------------------------------------------------------------------
+// QUEUE / STACK (queue.cpp, stack.cpp): one ring for both (common.hpp, QUEUE /
+// STACK).  `head` and `tail` are u64 tickets in the ring's header line; the
+// element with ticket t lives in slot t % max_entries; count = tail - head.
+//
+// A parallel launch sees one kind of access per map (the loader's call-site
+// analysis and vm_api.cpp's launch check: add-only, remove-only or peek-only),
+// so only one end moves while it runs and nothing reads a slot that a push of
+// the same launch claimed.  The calling lanes of a wave that name the same
+// map form a group; its first lane claims `take` tickets for all of them with
+// one agent-scope compare-and-swap on the moving end (the scope rb_reserve
+// uses) -- retried only when another wave moved that end, never waiting for a
+// value another lane must produce -- and the group's lanes, ranked by lane
+// id, take one ticket each; those past `take` fail as the serial run's
+// pushes onto a full ring / pops from an empty one do.  The end that stands
+// still is read with a plain agent-scope load.
+//
+// ORDERED batches (`exact`: one lane) run the reference's sequence -- mixed
+// operations, BPF_EXIST evictions -- reading both ends at the coherence point,
+// where the lane's own earlier atomics were performed.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ uint64_t qs_coh64(uint64_t a) {
+  return __hip_atomic_fetch_add(G64(a), 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void qs_set64(uint64_t a, uint64_t v) {
+  __hip_atomic_exchange(G64(a), (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ bool qs_cas64(uint64_t a, unsigned long long *expect, uint64_t want) {
+  return __hip_atomic_compare_exchange_strong(G64(a), expect, (unsigned long long)want, __ATOMIC_RELAXED,
+                                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The slot `o` (< 64) tickets after the one whose slot index is `bm` (<
+// max_entries, which is no power of two in general)
+__device__ __forceinline__ uint64_t qs_slot_after(const DMap &m, uint32_t bm, uint32_t o) {
+  uint64_t x = (uint64_t)bm + o;
+  if (x >= m.max_entries) {
+    x -= m.max_entries;
+    if (x >= m.max_entries) x = (uint32_t)x % m.max_entries;  // (x < 64 here)
+  }
+  return m.data + m.val_off + x * m.slot_size;
+}
+
+// The calling lanes that name one ring (helper_qs groups them).  op: the
+// helper id --
+//   87 bpf_map_push_elem(map, value, flags)  queue.cpp:128-169, stack.cpp:119-157
+//   88 bpf_map_pop_elem(map, value)          queue.cpp:171-194, stack.cpp:159-182
+//   89 bpf_map_peek_elem(map, value)         queue.cpp:196-215, stack.cpp:184-204
+//    1 lookup: a peek that returns the slot   queue.cpp:52-64,   stack.cpp:46-59
+//    2 update: a push, flags not validated    queue.cpp:66-105,  stack.cpp:61-97
+//    3 delete: a pop that discards (value 0)  queue.cpp:107-120, stack.cpp:99-111
+__device__ uint64_t qs_group(const DMap m, uint64_t value, uint64_t flags, uint32_t op, bool exact) {
+  const bool lifo = m.type == MT_STACK, push = op == 87 || op == 2, remove = op == 88 || op == 3;
+  const uint64_t ha = qs_head_addr(m), ta = qs_tail_addr(m), cap = m.max_entries, fail = op == 1 ? 0 : (uint64_t)-1;
+  // EINVAL: a NULL value; flags other than BPF_ANY (0) / BPF_EXIST (2) on a push
+  const bool ok = (op == 1 || op == 3 || value != 0) && (op != 87 || flags == 0 || flags == 2);
+  if (exact) {
+    if (!ok) return fail;
+    uint64_t h = qs_coh64(ha);
+    const uint64_t t = qs_coh64(ta);
+    if (push) {
+      if (t - h >= cap) {
+        if (flags != 2) return fail;  // E2BIG
+        qs_set64(ha, ++h);            // the oldest element: the queue's head, the stack's bottom
+      }
+      copy_bytes_publish(qs_slot(m, t), value, m.value_size);
+      qs_set64(ta, t + 1);
+      return 0;
+    }
+    if (t == h) return fail;  // ENOENT
+    const uint64_t s = qs_slot(m, lifo ? t - 1 : h);
+    if (op == 1) return s;
+    if (value) copy_bytes(value, s, m.value_size);
+    if (remove) {
+      if (lifo) qs_set64(ta, t - 1);
+      else qs_set64(ha, h + 1);
+    }
+    return 0;
+  }
+  const uint64_t grp = __ballot(ok);
+  if (!ok) return fail;
+  const uint32_t me = __lane_id(), leader = (uint32_t)__builtin_ctzll(grp);
+  const uint32_t n = (uint32_t)__builtin_popcountll(grp);
+  const uint32_t rank = (uint32_t)__builtin_popcountll(grp & ((1ull << me) - 1));
+  if (!push && !remove) {  // peek-only launch: nothing moves
+    const uint64_t h = ald64(ha), t = ald64(ta);
+    if (t == h) return fail;
+    const uint64_t s = qs_slot(m, lifo ? t - 1 : h);
+    if (op == 1) return s;
+    copy_bytes(value, s, m.value_size);
+    return 0;
+  }
+  // (a parallel push is a flags-0 push: the launch check admits no other)
+  uint32_t take = 0, bm = 0;
+  if (me == leader) {
+    unsigned long long h = ald64(ha), t = ald64(ta);
+    uint64_t base;
+    if (push) {  // add-only launch: `head` stands still
+      for (;;) {
+        const uint64_t used = t - h;
+        take = used >= cap ? 0 : (uint32_t)(cap - used < n ? cap - used : n);
+        if (!take || qs_cas64(ta, &t, t + take)) break;
+      }
+      base = t;
+    } else if (lifo) {  // remove-only launch, downward on `tail`
+      for (;;) {
+        take = (uint32_t)(t - h < n ? t - h : n);
+        if (!take || qs_cas64(ta, &t, t - take)) break;
+      }
+      base = t - take;
+    } else {  // remove-only launch, upward on `head`
+      for (;;) {
+        take = (uint32_t)(t - h < n ? t - h : n);
+        if (!take || qs_cas64(ha, &h, h + take)) break;
+      }
+      base = h;
+    }
+    bm = (uint32_t)(base % cap);
+  }
+  take = __shfl(take, leader);
+  bm = __shfl(bm, leader);
+  if (rank >= take) return fail;  // E2BIG / ENOENT
+  // tickets base .. base + take - 1: pushes and a queue's pops in rank
+  // order, a stack's pops from the top down
+  const uint64_t s = qs_slot_after(m, bm, push || !lifo ? rank : take - 1 - rank);
+  if (push) copy_bytes_publish(s, value, m.value_size);
+  else if (value) copy_bytes(value, s, m.value_size);
+  return 0;
+}
+
+// The QUEUE / STACK helpers' one entry (interp.hip call_helper sends helpers
+// 87 / 88 / 89 and 1 / 2 / 3 here when the map is a QUEUE / STACK; fd <
+// kMaxFds): one group per distinct map among the calling lanes, as
+// rb_reserve groups by ring.
+__device__ __noinline__ uint64_t helper_qs(const DMap *maps, uint64_t fd, uint64_t value, uint64_t flags,
+                                           uint32_t op, bool exact) {
+  const uint64_t all = __ballot(1);
+  uint64_t done = 0, out = 0;
+  while (all & ~done) {
+    const uint64_t f0 = __shfl(fd, (uint32_t)__builtin_ctzll(all & ~done));
+    if (fd == f0) out = qs_group(maps[fd], value, flags, op, exact);
+    done |= __ballot(fd == f0);
+  }
+  return out;
 }
 
 __device__ uint64_t helper_lookup(const DMap *maps, uint64_t fd, uint64_t key, LaneEnv &env) {

@@ -38,9 +38,9 @@
 namespace bpftime_amd {
 
 // Helper dispatch (helper id is wave-uniform); returns r0, sets *err.
-// BLOOM: the Bloom filter helpers are compiled in.  Only the scratch-stack
-// instances of k_interp and k_sys_seq carry them (the loader sends every
-// program that may reach a Bloom filter there, loader.cpp load_program): in
+// BLOOM: the Bloom filter and QUEUE / STACK helpers are compiled in.  Only the
+// scratch-stack instances of k_interp and k_sys_seq carry them (the loader
+// sends every program that may reach such a map there, loader.cpp load_program): in
 // the LDS-stack instances the call to them cost the headline path 2 %
 // (Bloom filters).
 template <bool BLOOM>
@@ -48,9 +48,16 @@ __device__ __forceinline__ uint64_t call_helper(uint32_t id, uint64_t a1, uint64
                                                 uint64_t a5, const DMap *maps, uint32_t ncpu, uint64_t seed,
                                                 LaneEnv &env, uint32_t *err) {
   if constexpr (BLOOM) {
+    // a QUEUE / STACK map: push / pop / peek, and lookup (a peek that returns
+    // the slot), update (a push, the key ignored) and delete (a pop that
+    // discards) -- dev_helpers.hpp helper_qs
+    const uint32_t mt = a1 < kMaxFds ? maps[a1].type : 0;
+    const bool elem = id == 87 || id == 88 || id == 89;
+    if (qs_type(mt) && (elem || id == 1 || id == 2 || id == 3))
+      return helper_qs(maps, a1, id == 2 ? a3 : elem ? a2 : 0, id == 2 ? a4 : id == 87 ? a3 : 0, id, env.exact);
     // bpf_map_push / pop / peek_elem, and a Bloom filter's bpf_map_update_elem:
     // a push of the value, the key ignored
-    const bool upd = id == 2 && a1 < kMaxFds && maps[a1].type == MT_BLOOM_FILTER;
+    const bool upd = id == 2 && mt == MT_BLOOM_FILTER;
     if (id == 87 || id == 88 || id == 89 || upd)
       return helper_bloom(maps, a1, upd ? a3 : a2, upd ? a4 : id == 87 ? a3 : 0, id, env.exact);
   }

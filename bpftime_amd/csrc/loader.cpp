@@ -26,7 +26,7 @@ bool device_helper_supported(uint32_t id) {
     case 130: case 131: case 132: case 133:
     case 58: case 187:  // bpf_override_return / bpf_set_retval (syscall dispatch state)
     case 14:            // bpf_get_current_pid_tgid (recorded caller / launching thread)
-    case 87: case 88: case 89:  // bpf_map_push / pop / peek_elem (BLOOM_FILTER)
+    case 87: case 88: case 89:  // bpf_map_push / pop / peek_elem (QUEUE, STACK, BLOOM_FILTER)
     case kTailHelper:
       return true;
   }
@@ -501,9 +501,12 @@ int load_program(const RawInsn *code, size_t n, const std::map<size_t, size_t> &
         case 1:
           if (!lddw.map_by_fd) { err = at + ", map_by_fd not defined"; return -EINVAL; }
           imm = lddw.map_by_fd((uint32_t)cur.imm);
-          {  // a Bloom filter named by fd: helper 2 on it is a push
+          {  // a Bloom filter named by fd: helper 2 on it is a push; a QUEUE /
+             // STACK: helpers 1 / 2 / 3 are peek / push / pop
             Runtime &r = rt();
-            if (imm < kMaxFds && r.kind[imm] == HKind::MAP && r.maps[imm].type == MT_BLOOM_FILTER) out.bloom = true;
+            if (imm < kMaxFds && r.kind[imm] == HKind::MAP &&
+                (r.maps[imm].type == MT_BLOOM_FILTER || qs_type(r.maps[imm].type)))
+              out.bloom = true;
           }
           break;
         case 2:
@@ -645,8 +648,8 @@ int load_program(const RawInsn *code, size_t n, const std::map<size_t, size_t> &
   int depth = entries.empty() ? stack_depth(p, reach) : -1;  // an image: every program on a 512-B stack
   out.multi_entry = !entries.empty();
   out.entries = entries;
-  // (a program that may reach a Bloom filter runs in the scratch-stack
-  // kernels: only they carry the Bloom helpers, interp.hip call_helper)
+  // (a program that may reach a Bloom filter or a QUEUE / STACK runs in the
+  // scratch-stack kernels: only they carry those helpers, interp.hip call_helper)
   if (depth < 0 || depth > (int)kLdsStackMax || out.bloom) {
     out.big_stack = true;
     out.stack_size = kStackSize;
@@ -885,7 +888,10 @@ static bool pointer_kinds(const std::vector<DInsn> &p, const std::vector<uint8_t
       case X_CALL: {
         // r1-r5 survive (ubpf); a lookup on a bound map yields a nullable value pointer
         const PVal m = st[1];
-        st[0] = (d.hi == 1 && m.kind == P_MAPFD && map_rec(m.id)) ? PVal{P_MVNULL, 0, m.id} : kOther;
+        // (not of a QUEUE / STACK: the slot a peek returns is no element of a keyed value array)
+        st[0] = (d.hi == 1 && m.kind == P_MAPFD && map_rec(m.id) && !qs_type(map_rec(m.id)->type))
+                    ? PVal{P_MVNULL, 0, m.id}
+                    : kOther;
         break;
       }
       case X_LDDW: {
@@ -1015,8 +1021,8 @@ static void accesses(const std::vector<DInsn> &p, uint32_t i, const std::vector<
     case 2: arg(2); arg(3); map_values(); return;
     case 3: arg(2); map_values(); return;
     case 87: arg(2); map_values(); return;  // push: reads the value, sets the map's bits
-    case 88: return;                        // pop: fails on every map type there is
-    case 89: arg(2); return;                // peek: reads the value (never written back)
+    case 88: arg(2); map_values(); return;  // pop: writes the value, takes from the map (QUEUE / STACK)
+    case 89: arg(2); map_values(); return;  // peek: reads the value (Bloom filter) or writes it (QUEUE / STACK)
     case 28: arg(1); arg(3); return;
     case 130: arg(2); return;
     case 132: case 133: arg(1); return;
@@ -1107,8 +1113,11 @@ static void const_loads(const std::vector<DInsn> &p, const std::vector<uint8_t> 
       case X_CALL:
         switch (d.hi) {
           case 1: case 5: case 7: case 8: case 14: case 28: case 58: case 187: case 130:
-          case 131: case 132: case 133: case 44: case 65: case 88: case 89:
-            break;  // no array-map writes (ring memory, the unit's ctx, dispatch state; pop / peek write nothing)
+          case 131: case 132: case 133: case 44: case 65:
+            break;  // no array-map writes (ring memory, the unit's ctx, dispatch state)
+          case 88: case 89:  // pop / peek of a QUEUE / STACK write *value
+            writes.push_back(loc_of(p, st[2], 0, kUnknownLen));
+            break;
           case 2: case 3: case 87:  // the values of the map in r1
             if (st[1].kind == P_MAPFD) writes.push_back(Loc{Loc::MAPVAL, st[1].id, 0, kUnknownLen});
             else writes.push_back(Loc{Loc::ANY, -1, 0, 0});
@@ -1194,6 +1203,126 @@ static void lpm_write_sites(const std::vector<DInsn> &p, const std::vector<uint8
   }
 }
 
+// Call sites that may reach a QUEUE / STACK map (FastForm::qs_sites).  Helpers
+// 87 / 88 / 89 with r1 bound to another map type are not sites (a Bloom
+// filter's, or -ENOTSUP); with r1 unresolved they are, with fd -1.  Helpers
+// 1 / 2 / 3 with r1 unresolved stand for every QUEUE / STACK the program
+// names in an lddw, as an LPM trie's write sites do.  r1 resolves when every
+// path to the call loads it from an lddw map fd (directly or through register
+// copies); it may then name several maps.  A push's flags (r3 of
+// helper 87, r4 of helper 2) are proven 0 when the register's last definition
+// before the call is `mov r, 0` with no jump target in between.
+static void qs_call_sites(const std::vector<DInsn> &p, const std::vector<uint8_t> &lddw_src,
+                          const std::vector<std::vector<PVal>> *in, FastForm &out) {
+  const uint32_t n = (uint32_t)p.size();
+  std::vector<int32_t> named;
+  for (uint32_t i = 0; i < n; i++) {
+    if (p[i].op != X_LDDW || i >= lddw_src.size() || lddw_src[i] != 1) continue;
+    const uint64_t v = (uint64_t)(uint32_t)p[i].imm | ((uint64_t)(uint32_t)p[i].hi << 32);
+    const MapRec *m = v < kMaxFds ? map_rec((int64_t)v) : nullptr;
+    if (m && qs_type(m->type) && std::find(named.begin(), named.end(), (int32_t)v) == named.end())
+      named.push_back((int32_t)v);
+  }
+  std::vector<bool> is_target(n, false);
+  for (uint32_t i = 0; i < n; i++) {
+    if (p[i].op == X_BAD) continue;
+    uint32_t s[2];
+    int ns;
+    successors(p, i, s, ns);
+    for (int j = 0; j < ns; j++)
+      if (s[j] < n && s[j] != i + 1 && !(p[i].op == X_LDDW && s[j] == i + 2)) is_target[s[j]] = true;
+  }
+  auto zero_before = [&](uint32_t call, int reg) {
+    for (uint32_t j = call; j-- > 0;) {
+      if (is_target[j + 1]) return false;  // control may enter between the definition and the call
+      RegSet u, df;
+      use_def(p[j], u, df);
+      if (!(df & (1u << reg))) continue;
+      return p[j].op == X_MOV && !(p[j].aux & A_SRCREG) && p[j].imm == 0;
+    }
+    return false;
+  };
+  // the map fds r1 may hold at each pc: lddw map-fd constants and register
+  // copies, joined over the paths (a call site reached with r1 = one of two
+  // maps is a site of both); anything else is unknown
+  struct FdSet {
+    bool top = false;
+    std::vector<int32_t> fds;
+    bool join(const FdSet &o) {
+      if (top) return false;
+      if (o.top) {
+        top = true;
+        return true;
+      }
+      bool ch = false;
+      for (const int32_t f : o.fds)
+        if (std::find(fds.begin(), fds.end(), f) == fds.end()) {
+          fds.push_back(f);
+          ch = true;
+        }
+      return ch;
+    }
+  };
+  FdSet unknown;
+  unknown.top = true;
+  std::vector<std::vector<FdSet>> at(n);
+  if (in && n) {
+    std::vector<uint32_t> work{0};
+    at[0].assign(11, unknown);
+    while (!work.empty()) {
+      const uint32_t i = work.back();
+      work.pop_back();
+      if (p[i].op == X_BAD) continue;
+      std::vector<FdSet> st = at[i];
+      const DInsn &d = p[i];
+      if (d.op == X_LDDW && i < lddw_src.size() && lddw_src[i] == 1) {
+        st[d.dst] = FdSet{};
+        st[d.dst].fds.push_back((int32_t)(uint32_t)d.imm);
+      } else if (d.op == X_MOV && (d.aux & A_SRCREG) && !(d.aux & A_W32)) {
+        st[d.dst] = st[d.src];
+      } else {
+        RegSet u, df;
+        use_def(d, u, df);
+        for (int r = 0; r < 11; r++)
+          if (df & (1u << r)) st[r] = unknown;
+      }
+      uint32_t sx[2];
+      int ns;
+      successors(p, i, sx, ns);
+      for (int j = 0; j < ns; j++) {
+        const uint32_t t = sx[j];
+        if (t >= n) continue;
+        bool ch = at[t].empty();
+        if (ch) at[t] = st;
+        else
+          for (int r = 0; r < 11; r++) ch = at[t][r].join(st[r]) || ch;
+        if (ch) work.push_back(t);
+      }
+    }
+  }
+  for (uint32_t i = 0; i < n; i++) {
+    if (p[i].op != X_CALL) continue;
+    const uint32_t h = (uint32_t)p[i].hi;
+    const bool elem = h == 87 || h == 88 || h == 89;
+    if (!elem && h != 1 && h != 2 && h != 3) continue;
+    const bool flags0 = h == 87 ? zero_before(i, 3) : h == 2 ? zero_before(i, 4) : true;
+    if (in) {
+      const PVal &r1 = (*in)[i][1];
+      if (r1.kind == P_UNDEF && (*in)[i][0].kind == P_UNDEF) continue;  // unreachable
+      if (!at[i].empty() && !at[i][1].top) {
+        for (const int32_t fd : at[i][1].fds) {
+          const MapRec *m = map_rec(fd);
+          if (m && qs_type(m->type)) out.qs_sites.push_back({h, fd, flags0});
+        }
+        continue;
+      }
+    }
+    if (elem) out.qs_sites.push_back({h, -1, flags0});
+    else
+      for (const int32_t fd : named) out.qs_sites.push_back({h, fd, flags0});
+  }
+}
+
 // The ctx and stack words a linked target may write (FastForm
 // tail_ctx_mask / tail_stack_mask): its stores through ctx / stack pointers
 // of known offset, and the helpers that write ctx fields or stack buffers.
@@ -1235,8 +1364,8 @@ static void tail_save_masks(const std::vector<DInsn> &p, const std::vector<std::
     if (d.op != X_CALL) continue;
     switch ((uint32_t)d.hi) {
       case 1: case 2: case 3: case 5: case 7: case 8: case 12: case 28: case 130: case 131: case 132: case 133:
-      case 87: case 88: case 89:  // push / pop / peek: no write to unit memory (peek leaves *value)
-        break;
+      case 87: break;  // push: no write to unit memory
+      case 88: case 89: write(st[2], 0, 1 << 16); break;  // pop / peek of a QUEUE / STACK write *value
       case 44: case 65: ctx_bytes(0, 16); break;  // adjust_head / adjust_tail: data, data_end
       case 189: write(st[3], 0, 1 << 16); break;  // xdp_load_bytes(ctx, off, to, len)
       default:
@@ -1333,8 +1462,7 @@ static void map_effects(const std::vector<DInsn> &prog, const std::vector<std::v
         const int32_t fd = m.kind == P_MAPFD ? m.id : -1;
         switch (d.hi) {
           case 1: case 89: mark(fd, FX_READ); break;                    // map_lookup_elem, map_peek_elem
-          case 2: case 3: case 130: case 131: case 87: mark(fd, FX_WRITE); break;  // update, delete, ringbuf output / reserve, push
-          case 88:  // map_pop_elem: fails without touching the map
+          case 2: case 3: case 130: case 131: case 87: case 88: mark(fd, FX_WRITE); break;  // update, delete, ringbuf output / reserve, push, pop
           case 5: case 7: case 8: case 14: case 28: case 44: case 58: case 65: case 132: case 133: case 187: case 189:
             break;  // no map effects (132 / 133 finish a reservation 131 marked)
           default: mark(-1, FX_READ | FX_WRITE); break;                 // bpf_tail_call, anything else
@@ -1404,6 +1532,7 @@ void build_fast(const LoadOut &lo, bool xdp, FastForm &out) {
     kinds_ok = pointer_kinds(prog, lo.lddw_src, xdp, pkt_ok, in);
   }
   lpm_write_sites(prog, lo.lddw_src, kinds_ok ? &in : nullptr, out);
+  qs_call_sites(prog, lo.lddw_src, kinds_ok ? &in : nullptr, out);
   // may a store reach the memory r1 points to at entry (the unit: the
   // syscall dispatch runs such a program on a copy of its records, as each
   // reference callback gets its own ctx copy)

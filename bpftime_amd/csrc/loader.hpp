@@ -65,6 +65,18 @@ struct FastForm {
   // batches (dev_helpers.hpp lpm_update); vm_api.cpp refuses other batches
   std::vector<std::pair<uint32_t, int32_t>> lpm_writes;
   bool names_lpm = false;  // an lddw names an LPM trie (its launches take the LPM launch lock)
+  // call sites that may reach a QUEUE / STACK map: helpers 87 / 88 / 89 and
+  // 1 / 2 / 3.  fd: the map the pointer kinds bind r1 to, or -1 when they
+  // cannot resolve it (helpers 1 / 2 / 3 then stand for every QUEUE / STACK
+  // the program names in an lddw, one site each).  flags0: a push (87 / 2)
+  // whose flags register is proven 0.  A parallel launch needs every such map
+  // add-only, remove-only or peek-only (vm_api.cpp qs_launch_check)
+  struct QsSite {
+    uint32_t helper;
+    int32_t fd;
+    bool flags0;
+  };
+  std::vector<QsSite> qs_sites;
   // a store may reach the unit r1 points to at entry (the pointer kinds
   // cannot place every store on the stack, a map value or a constant)
   bool stores_unit = true;
@@ -83,7 +95,7 @@ struct LoadOut {
   bool big_stack = false;    // 512-B scratch stack
   uint32_t fused_rmw = 0;
   uint32_t comb_entries = 0;  // per-block LDS combining entries (0 = none needed)
-  bool bloom = false;         // calls bpf_map_push / pop / peek_elem or names a BLOOM_FILTER: scratch-stack kernels only
+  bool bloom = false;         // calls bpf_map_push / pop / peek_elem or names a BLOOM_FILTER / QUEUE / STACK: scratch-stack kernels only
   bool may_delete = false;    // calls map_delete_elem: hash lookup indexes stop being valid
   bool tail_call = false;     // calls bpf_tail_call: linked with the prog arrays' targets at launch
   bool sets_retval = false;   // calls bpf_override_return (58) / bpf_set_retval (187)

@@ -74,10 +74,12 @@ static int array_next_key(MapRec &m, int, const void *key, void *next_key) {  //
 
 const MapOps kArrayOps = {
     array_create, array_lookup, array_update, array_erase, array_next_key,
-    /*percpu=*/false, /*counter_line=*/false, /*lru_stamps=*/false, /*prog_shadow=*/false, /*lookup_index=*/false};
+    /*percpu=*/false, /*counter_line=*/false, /*lru_stamps=*/false, /*prog_shadow=*/false, /*lookup_index=*/false,
+    map_no_push, map_no_pop, map_no_peek};
 const MapOps kPercpuArrayOps = {
     array_create, array_lookup, array_update, array_erase, array_next_key,
-    /*percpu=*/true, /*counter_line=*/false, /*lru_stamps=*/false, /*prog_shadow=*/false, /*lookup_index=*/false};
+    /*percpu=*/true, /*counter_line=*/false, /*lru_stamps=*/false, /*prog_shadow=*/false, /*lookup_index=*/false,
+    map_no_push, map_no_pop, map_no_peek};
 
 // ---- host views of ARRAY maps (bpftime_shm.cpp:347-353 via the mocked
 // mmap64, syscall_context.cpp:915-920) ---------------------------------------

@@ -84,44 +84,31 @@ static int bloom_next_key(MapRec &, int, const void *, void *) {
   return -1;
 }
 
+static long bloom_push_elem(MapRec &m, const void *value, uint64_t flags) {
+  if (flags != 0) {  // bloom_filter.cpp:346-352: BPF_ANY only
+    errno = EINVAL;
+    return -1;
+  }
+  return bloom_host_op(m, value, true);
+}
+
+static long bloom_peek_elem(MapRec &m, void *value) { return bloom_host_op(m, value, false); }
+
+static long bloom_pop_elem(MapRec &, void *) {
+  errno = EOPNOTSUPP;  // bloom_filter.cpp:364-369
+  return -1;
+}
+
 const MapOps kBloomFilterOps = {
     bloom_create, bloom_lookup, bloom_update, bloom_erase, bloom_next_key,
-    /*percpu=*/false, /*counter_line=*/false, /*lru_stamps=*/false, /*prog_shadow=*/false, /*lookup_index=*/false};
+    /*percpu=*/false, /*counter_line=*/false, /*lru_stamps=*/false, /*prog_shadow=*/false, /*lookup_index=*/false,
+    bloom_push_elem, bloom_pop_elem, bloom_peek_elem};
 
 }  // namespace bpftime_amd
 
 using namespace bpftime_amd;
 
 extern "C" {
-
-// bpftime_shm.cpp:168-200 over map_handler.cpp:1378-1468: -ENOTSUP for a map
-// type without the operation (there are no QUEUE / STACK maps here)
-long bpftime_map_push_elem(int fd, const void *value, uint64_t flags) {
-  MapRec *m = map_of(fd);
-  if (!m) return -1;
-  if (m->type != MT_BLOOM_FILTER) return -ENOTSUP;
-  if (flags != 0) {  // bloom_filter.cpp:346-352: BPF_ANY only
-    errno = EINVAL;
-    return -1;
-  }
-  return bloom_host_op(*m, value, true);
-}
-
-long bpftime_map_peek_elem(int fd, void *value) {
-  MapRec *m = map_of(fd);
-  if (!m) return -1;
-  if (m->type != MT_BLOOM_FILTER) return -ENOTSUP;
-  return bloom_host_op(*m, value, false);
-}
-
-long bpftime_map_pop_elem(int fd, void *value) {
-  MapRec *m = map_of(fd);
-  (void)value;
-  if (!m) return -1;
-  if (m->type != MT_BLOOM_FILTER) return -ENOTSUP;
-  errno = EOPNOTSUPP;  // bloom_filter.cpp:364-369
-  return -1;
-}
 
 int bpftime_amd_bloom_seed(int fd, const uint32_t *set, uint32_t *out) {
   Runtime &r = rt();

@@ -180,10 +180,12 @@ static int hash_next_key(MapRec &m, int, const void *key, void *next_key) {  // 
 
 const MapOps kHashOps = {
     hash_create, hash_lookup, hash_update, hash_erase<false>, hash_next_key,
-    /*percpu=*/false, /*counter_line=*/true, /*lru_stamps=*/false, /*prog_shadow=*/false, /*lookup_index=*/true};
+    /*percpu=*/false, /*counter_line=*/true, /*lru_stamps=*/false, /*prog_shadow=*/false, /*lookup_index=*/true,
+    map_no_push, map_no_pop, map_no_peek};
 const MapOps kPercpuHashOps = {
     hash_create, hash_lookup, percpu_hash_update, hash_erase<true>, hash_next_key,
-    /*percpu=*/true, /*counter_line=*/true, /*lru_stamps=*/false, /*prog_shadow=*/false, /*lookup_index=*/true};
+    /*percpu=*/true, /*counter_line=*/true, /*lru_stamps=*/false, /*prog_shadow=*/false, /*lookup_index=*/true,
+    map_no_push, map_no_pop, map_no_peek};
 
 // ---- the lookup index -------------------------------------------------------
 void ix_invalidate(int fd) {

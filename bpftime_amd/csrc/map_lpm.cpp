@@ -269,7 +269,8 @@ static int lpm_next_key(MapRec &m, int fd, const void *key, void *next_key) {
 
 const MapOps kLpmTrieOps = {
     lpm_create, lpm_lookup, lpm_update, lpm_erase, lpm_next_key,
-    /*percpu=*/false, /*counter_line=*/false, /*lru_stamps=*/false, /*prog_shadow=*/false, /*lookup_index=*/false};
+    /*percpu=*/false, /*counter_line=*/false, /*lru_stamps=*/false, /*prog_shadow=*/false, /*lookup_index=*/false,
+    map_no_push, map_no_pop, map_no_peek};
 
 }  // namespace bpftime_amd
 

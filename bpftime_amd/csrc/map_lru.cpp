@@ -206,7 +206,8 @@ static int lru_host_next_key(MapRec &m, int, const void *key, void *next_key) {
 
 const MapOps kLruHashOps = {
     lru_create, lru_host_lookup, lru_host_update, lru_host_delete, lru_host_next_key,
-    /*percpu=*/false, /*counter_line=*/true, /*lru_stamps=*/true, /*prog_shadow=*/false, /*lookup_index=*/false};
+    /*percpu=*/false, /*counter_line=*/true, /*lru_stamps=*/true, /*prog_shadow=*/false, /*lookup_index=*/false,
+    map_no_push, map_no_pop, map_no_peek};
 
 uint64_t Runtime::prepare_lru() {
   std::lock_guard<std::mutex> g(mu);

@@ -28,10 +28,18 @@ struct MapOps {
   // + a u64 stamp per bucket (the map joins Runtime::lru_maps); a second
   // copy of the slots, both INVALID_ENTRY (-1); a hash lookup index
   bool counter_line, lru_stamps, prog_shadow, lookup_index;
+  // bpf_map_push / pop / peek_elem (map_handler.cpp:1378-1468): QUEUE, STACK
+  // and BLOOM_FILTER; every other type's entries answer -ENOTSUP (map_no_*)
+  long (*push_elem)(MapRec &, const void *value, uint64_t flags);
+  long (*pop_elem)(MapRec &, void *value);
+  long (*peek_elem)(MapRec &, void *value);
 };
+long map_no_push(MapRec &, const void *, uint64_t);
+long map_no_pop(MapRec &, void *);
+long map_no_peek(MapRec &, void *);
 const MapOps *map_ops(uint32_t type);  // nullptr: no such map type
 extern const MapOps kArrayOps, kPercpuArrayOps, kHashOps, kPercpuHashOps, kLruHashOps, kLpmTrieOps, kProgArrayOps,
-    kRingbufOps, kBloomFilterOps;
+    kRingbufOps, kBloomFilterOps, kQueueOps, kStackOps;
 
 // the one lookup buffer of a thread, shared by every map type
 extern thread_local std::vector<uint8_t> tl_lookup_buf;
@@ -97,6 +105,9 @@ inline void write_count(const MapRec &m, uint64_t c) { write_word(m, 0, c); }
 int hash_geometry(MapRec &m, uint64_t want_buckets, uint64_t value_bytes);
 // probe like bpftime_hash_map::elem_lookup; returns bucket or -1
 int64_t host_hash_find(const MapRec &m, const void *key, std::vector<uint8_t> &slot, int64_t *first_empty);
+
+// map_queue.cpp: a QUEUE / STACK map's element count (tail - head)
+uint64_t qs_count(const MapRec &m);
 
 // map_lpm.cpp: the LPM half of Runtime::prepare_ix (its arguments; the caller
 // holds the runtime lock)

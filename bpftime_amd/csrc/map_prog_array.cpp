@@ -97,6 +97,7 @@ static int prog_array_next_key(MapRec &m, int, const void *key, void *next_key) 
 
 const MapOps kProgArrayOps = {
     prog_array_create, prog_array_lookup, prog_array_update, prog_array_delete, prog_array_next_key,
-    /*percpu=*/false, /*counter_line=*/false, /*lru_stamps=*/false, /*prog_shadow=*/true, /*lookup_index=*/false};
+    /*percpu=*/false, /*counter_line=*/false, /*lru_stamps=*/false, /*prog_shadow=*/true, /*lookup_index=*/false,
+    map_no_push, map_no_pop, map_no_peek};
 
 }  // namespace bpftime_amd

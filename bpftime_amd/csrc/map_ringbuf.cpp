@@ -37,7 +37,8 @@ static int ringbuf_next_key(MapRec &, int, const void *, void *) {
 
 const MapOps kRingbufOps = {
     ringbuf_create, ringbuf_lookup, ringbuf_update, ringbuf_erase, ringbuf_next_key,
-    /*percpu=*/false, /*counter_line=*/false, /*lru_stamps=*/false, /*prog_shadow=*/false, /*lookup_index=*/false};
+    /*percpu=*/false, /*counter_line=*/false, /*lru_stamps=*/false, /*prog_shadow=*/false, /*lookup_index=*/false,
+    map_no_push, map_no_pop, map_no_peek};
 
 }  // namespace bpftime_amd
 

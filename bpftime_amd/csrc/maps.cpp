@@ -37,9 +37,17 @@ const MapOps *map_ops(uint32_t type) {
     case MT_PROG_ARRAY: return &kProgArrayOps;
     case MT_RINGBUF: return &kRingbufOps;
     case MT_BLOOM_FILTER: return &kBloomFilterOps;
+    case MT_QUEUE: return &kQueueOps;
+    case MT_STACK: return &kStackOps;
   }
   return nullptr;
 }
+
+// map_handler.cpp:1404-1407, :1431-1434, :1463-1466: a map type without the
+// operation
+long map_no_push(MapRec &, const void *, uint64_t) { return -ENOTSUP; }
+long map_no_pop(MapRec &, void *) { return -ENOTSUP; }
+long map_no_peek(MapRec &, void *) { return -ENOTSUP; }
 
 }  // namespace bpftime_amd
 
@@ -161,6 +169,22 @@ int bpftime_map_get_next_key(int fd, const void *key, void *next_key) {
   return m ? map_ops(m->type)->next_key(*m, fd, key, next_key) : -1;
 }
 
+// bpftime_shm.cpp:168-200 over map_handler.cpp:1378-1468
+long bpftime_map_push_elem(int fd, const void *value, uint64_t flags) {
+  MapRec *m = map_of(fd);
+  return m ? map_ops(m->type)->push_elem(*m, value, flags) : -1;
+}
+
+long bpftime_map_pop_elem(int fd, void *value) {
+  MapRec *m = map_of(fd);
+  return m ? map_ops(m->type)->pop_elem(*m, value) : -1;
+}
+
+long bpftime_map_peek_elem(int fd, void *value) {
+  MapRec *m = map_of(fd);
+  return m ? map_ops(m->type)->peek_elem(*m, value) : -1;
+}
+
 // ---- lddw helpers: bpftime_shm.cpp:637-676 --------------------------------
 uint64_t bpftime_amd_map_ptr_by_fd(uint32_t fd) {
   if (!map_of((int)fd)) {
@@ -243,9 +267,12 @@ uint64_t bpftime_amd_map_count(int fd) {
     std::lock_guard<std::mutex> g(rt().mu);
     return lpm_pull(fd) < 0 ? 0 : m->lpm->entries;
   }
+  if (m && qs_type(m->type)) return qs_count(*m);
   if (!m || !m->d.count_addr) return 0;
   return read_count(*m);
 }
+
+int bpftime_amd_map_type_supported(uint32_t type) { return map_ops(type) ? 1 : 0; }
 
 // ---- map info (bpftime_shm.cpp:287-306) -------------------------------------
 int bpftime_map_get_info(int fd, struct bpf_map_attr *out_attr, const char **out_name, int *type) {

@@ -132,6 +132,13 @@ struct Runtime {
   std::mutex lpm_launch_mu;
   std::atomic<int> lpm_maps{0};
   std::atomic<bool> lpm_inflight{false}, lpm_writer_inflight{false};
+  // QUEUE / STACK maps (vm_api.cpp qs_launch_check): launches that may still
+  // run and add to one / remove from or peek one.  A launch that removes from
+  // or peeks a map never overlaps one that adds to a map, on any stream:
+  // whichever comes second waits for the device first.  An ORDERED launch
+  // that touches such a map sets and honours both flags (its lane moves the
+  // ends without compare-and-swap), so it overlaps no other such launch
+  std::atomic<bool> qs_adder_inflight{false}, qs_taker_inflight{false};
   std::set<int> lru_maps;                // LRU_HASH maps
   std::atomic<uint64_t> lru_seq{1};      // LRU stamp sequence: launches and host-side ops (common.hpp)
   uint32_t lru_launches = 0;             // launches since the last tombstone check
@@ -165,6 +172,10 @@ void syscall_detach_all();
 // raw entry form): per map fd FX_* bits and the bits that may reach any map.
 // -1: no program loaded.
 int vm_map_effects(const ::ebpf_vm *vm, std::map<int32_t, uint8_t> &fx, uint8_t &any);
+// Whether a loaded program may reach a QUEUE / STACK map (loader.cpp
+// qs_call_sites): such a program does not commute with itself across
+// records, so the syscall dispatch runs it only in ORDERED dispatches.
+bool vm_touches_qs(const ::ebpf_vm *vm);
 // The thread-ordered syscall dispatch's launch (interp.hip k_sys_seq):
 // `progs` in the reference's order (syscall_dispatch.cpp), over n device
 // records laid out as `lay`; thread t's records perm[seg[t] .. seg[t + 1])

@@ -170,6 +170,12 @@ int conflicts(const std::vector<Attach> &order) {
 // 1 thread-ordered, 0 program-major, -1 error
 int plan_for(const std::vector<Attach> &order, uint32_t flags) {
   if (flags & EBPF_BATCH_ORDERED) return 1;  // one lane, record order: the serial run
+  // a program that pushes to or pops from a QUEUE / STACK does not commute,
+  // and lanes in thread order are not record order across threads
+  for (const Attach &a : order)
+    if (bpftime_amd::vm_touches_qs(a.vm.get()))
+      return fail("an attached program touches a QUEUE / STACK map: the dispatch runs it only with EBPF_BATCH_ORDERED",
+                  EINVAL);
   if (flags & BPFTIME_AMD_DISPATCH_PROGRAMS) return 0;
   if (flags & BPFTIME_AMD_DISPATCH_THREADS) return 1;
   const int c = conflicts(order);

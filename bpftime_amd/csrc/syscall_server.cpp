@@ -81,9 +81,15 @@ extern "C" long bpftime_amd_handle_sysbpf(int cmd, void *attr_, uint32_t size) {
     case BPF_MAP_FREEZE:  // :669-678: accepted, not implemented
       return 0;
     case BPF_MAP_LOOKUP_AND_DELETE_ELEM:  // :540-551 -> bpf_map_handler::map_pop_elem
-      // (map_handler.cpp:1411-1434): queue / stack maps only, -ENOTSUP for
-      // every other map type; -1 for an fd without a map handler
+      // (map_handler.cpp:1411-1434): a pop for queue / stack maps, -ENOTSUP
+      // for every other map type; -1 for an fd without a map handler
       if (!bpftime_is_map_fd((int)attr->map_fd)) return -1;
+      {
+        int type = 0;
+        if (bpftime_map_get_info((int)attr->map_fd, nullptr, nullptr, &type) == 0 &&
+            (type == BPF_MAP_TYPE_QUEUE || type == BPF_MAP_TYPE_STACK))
+          return bpftime_map_pop_elem((int)attr->map_fd, (void *)(uintptr_t)attr->value);
+      }
       return -ENOTSUP;
     case BPF_OBJ_GET_INFO_BY_FD: {  // :679-722
       const int fd = (int)attr->info.bpf_fd;

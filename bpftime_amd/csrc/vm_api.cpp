@@ -29,6 +29,91 @@
 namespace bpftime_amd {
 extern "C" hipError_t bpftime_amd_launch_interp(const KParams *p, uint32_t kind, bool big_stack, uint32_t grid,
                                                 uint32_t ordered, uint32_t block, hipStream_t stream);
+
+// QUEUE / STACK maps in a launch of the program form `f` (loader.cpp
+// qs_call_sites).  The device's parallel push / pop / peek are correct only
+// while one map sees one kind of access during a launch (dev_helpers.hpp
+// qs_group): each map must be add-only (helpers 87 / 2 with flags proven 0),
+// remove-only (88 / 3) or peek-only (89 / 1).  Anything else -- mixed kinds on
+// one map, a push with flags that are not proven 0, helpers 87 / 88 / 89 on a
+// map register the loader cannot resolve while any QUEUE / STACK map exists --
+// runs only in EBPF_BATCH_ORDERED batches (one lane, the reference's
+// sequence).  `adds` / `takes`: the launch may add to such a map / remove from
+// or peek one (Runtime::qs_adder_inflight).  An ORDERED launch that touches
+// such a map counts as both, whatever its call sites do: its one lane moves
+// `head` / `tail` with a read and an unconditional exchange, not with the
+// parallel paths' compare-and-swap, so it must overlap no other launch that
+// touches a QUEUE / STACK -- not even one of its own kind.
+static bool qs_launch_check(const FastForm &f, bool ordered, std::string &error, bool &adds, bool &takes) {
+  adds = takes = false;
+  if (f.qs_sites.empty()) return true;
+  Runtime &r = rt();
+  static const char *const kRule =
+      ": in a parallel batch each QUEUE / STACK map must be add-only (push / update with flags 0), remove-only "
+      "(pop / delete) or peek-only (peek / lookup); this program runs only in EBPF_BATCH_ORDERED batches";
+  auto name = [](uint32_t h) {
+    switch (h) {
+      case 1: return "bpf_map_lookup_elem";
+      case 2: return "bpf_map_update_elem";
+      case 3: return "bpf_map_delete_elem";
+      case 87: return "bpf_map_push_elem";
+      case 88: return "bpf_map_pop_elem";
+    }
+    return "bpf_map_peek_elem";
+  };
+  auto is_qs = [&](int32_t fd) {
+    return fd >= 0 && fd < (int32_t)kMaxFds && r.kind[fd] == HKind::MAP && qs_type(r.maps[fd].type);
+  };
+  bool any_qs = false;
+  for (uint32_t fd = 0; fd < kMaxFds && !any_qs; fd++) any_qs = is_qs((int32_t)fd);
+  if (!any_qs) return true;
+  std::map<int32_t, std::pair<uint32_t, uint32_t>> modes;  // fd -> {kinds seen, the first site's helper}
+  for (const FastForm::QsSite &q : f.qs_sites) {
+    const uint32_t kind = (q.helper == 87 || q.helper == 2) ? 1u : (q.helper == 88 || q.helper == 3) ? 2u : 4u;
+    if (q.fd < 0) {
+      adds = takes = true;
+      if (ordered) continue;
+      error = std::string(name(q.helper)) + " on a map fd the loader cannot resolve (a QUEUE / STACK map exists)" +
+              kRule;
+      return false;
+    }
+    if (!is_qs(q.fd)) continue;
+    if (ordered) {
+      adds = takes = true;
+      continue;
+    }
+    (kind == 1 ? adds : takes) = true;
+    const std::string at = std::string(name(q.helper)) + " on " +
+                           (r.maps[q.fd].type == MT_STACK ? "STACK" : "QUEUE") + " map fd " + std::to_string(q.fd);
+    if (kind == 1 && !q.flags0) {
+      error = at + " with flags not proven 0" + kRule;
+      return false;
+    }
+    auto it = modes.find(q.fd);
+    if (it == modes.end()) {
+      modes[q.fd] = {kind, q.helper};
+    } else if (it->second.first != kind) {
+      error = at + " beside " + name(it->second.second) + " on the same map" + kRule;
+      return false;
+    }
+  }
+  return true;
+}
+
+// QUEUE / STACK launches on different streams: one that removes from or peeks
+// a map never overlaps one that adds to a map, and an ORDERED one (both, see
+// above) overlaps no other -- whichever comes second waits for the device
+// first (the lookup cache's rule, Runtime::lcache_inflight)
+static bool qs_launch_fence(bool adds, bool takes) {
+  Runtime &r = rt();
+  if ((takes && r.qs_adder_inflight.load()) || (adds && r.qs_taker_inflight.load())) {
+    if (hipDeviceSynchronize() != hipSuccess) return false;
+    r.qs_adder_inflight = false;
+    r.qs_taker_inflight = false;
+  }
+  return true;
+}
+
 extern "C" int bpftime_amd_occupancy(uint32_t kind, bool big_stack, size_t dyn_lds, bool gregs, uint32_t block,
                                     bool image);
 extern "C" size_t bpftime_amd_static_lds_image(uint32_t kind, bool big_stack, bool gregs, uint32_t block, bool image);
@@ -853,6 +938,14 @@ int Mi355xVm::exec_batch(const ebpf_batch *b) {
     }
     if (std::find(lpm_w.begin(), lpm_w.end(), w.second) == lpm_w.end()) lpm_w.push_back(w.second);
   }
+  // QUEUE / STACK maps: one kind of access per map in a parallel launch
+  bool qs_adds = false, qs_takes = false;
+  if (!qs_launch_check(kind == CTX_XDP ? im.fx : im.fr, (b->flags & EBPF_BATCH_ORDERED) != 0, error, qs_adds, qs_takes))
+    return -1;
+  if (!qs_launch_fence(qs_adds, qs_takes)) {
+    error = "device synchronize failed";
+    return -1;
+  }
   // the lookup cache trusts a found slot for the whole launch: no deletion
   // may run beside it (Runtime::lcache_inflight)
   if ((p.lcache && r.deleter_inflight.load()) || (prog.may_delete && r.lcache_inflight.load())) {
@@ -1061,6 +1154,8 @@ int Mi355xVm::exec_batch(const ebpf_batch *b) {
   }
   if (p.lcache) r.lcache_inflight = true;
   if (prog.may_delete) r.deleter_inflight = true;
+  if (qs_adds) r.qs_adder_inflight = true;
+  if (qs_takes) r.qs_taker_inflight = true;
   if (!lpm_w.empty()) {
     std::lock_guard<std::mutex> g(r.mu);
     for (const int fd : lpm_w) r.lpm_dev_dirty.insert(fd);
@@ -1203,6 +1298,16 @@ int vm_map_effects(const ::ebpf_vm *vm, std::map<int32_t, uint8_t> &fx, uint8_t 
   return 0;
 }
 
+bool vm_touches_qs(const ::ebpf_vm *vm) {
+  if (!vm || !vm->impl->loaded) return false;
+  auto im = vm->impl->image();
+  if (!im) return false;
+  std::string e;
+  bool adds = false, takes = false;
+  qs_launch_check(im->fr, true, e, adds, takes);
+  return adds || takes;
+}
+
 extern "C" hipError_t bpftime_amd_launch_sys_seq(const SeqParams *p, hipStream_t stream);
 
 int64_t seq_dispatch(const std::vector<SeqAttach> &progs, const SysLayout &lay, uint64_t n, const uint32_t *perm,
@@ -1219,7 +1324,7 @@ int64_t seq_dispatch(const std::vector<SeqAttach> &progs, const SysLayout &lay, 
   // another thread never frees what is read: Image, above)
   std::vector<std::shared_ptr<Image>> keep;
   const bool ordered = (flags & EBPF_BATCH_ORDERED) != 0;
-  bool may_delete = false, names_lpm = false;
+  bool may_delete = false, names_lpm = false, qs_adds = false, qs_takes = false;
   std::vector<int> lpm_w;
   uint32_t lpm_updates = 0;
   uint64_t steps = 0;
@@ -1260,6 +1365,16 @@ int64_t seq_dispatch(const std::vector<SeqAttach> &progs, const SysLayout &lay, 
     q.enter = a.enter ? 1 : 0;
     may_delete |= im->prog.may_delete;
     names_lpm |= im->fr.names_lpm;
+    {  // QUEUE / STACK maps: lanes in thread order are not record order across threads
+      std::string qe;
+      bool touches_add = false, touches_take = false;
+      qs_launch_check(im->fr, true, qe, touches_add, touches_take);
+      if ((touches_add || touches_take) && !ordered)
+        return fail("an attached program touches a QUEUE / STACK map: it does not commute and runs only in "
+                    "EBPF_BATCH_ORDERED dispatches");
+      qs_adds |= touches_add;
+      qs_takes |= touches_take;
+    }
     for (const auto &w : im->fr.lpm_writes) {
       if (!ordered)
         return fail(std::string(w.first == 2 ? "bpf_map_update_elem" : "bpf_map_delete_elem") +
@@ -1295,6 +1410,7 @@ int64_t seq_dispatch(const std::vector<SeqAttach> &progs, const SysLayout &lay, 
     r.lcache_inflight = false;
     r.deleter_inflight = false;
   }
+  if (!qs_launch_fence(qs_adds, qs_takes)) return fail("device synchronize failed");
   std::unique_lock<std::mutex> lpm_lk(r.lpm_launch_mu, std::defer_lock);
   const bool touches_lpm = r.lpm_maps.load() > 0 && names_lpm;
   if (touches_lpm) {
@@ -1316,6 +1432,8 @@ int64_t seq_dispatch(const std::vector<SeqAttach> &progs, const SysLayout &lay, 
   if (e == hipSuccess) e = bpftime_amd_launch_sys_seq(&p, s);
   if (e != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(e));
   if (may_delete) r.deleter_inflight = true;
+  if (qs_adds) r.qs_adder_inflight = true;
+  if (qs_takes) r.qs_taker_inflight = true;
   if (!lpm_w.empty()) {
     std::lock_guard<std::mutex> g(r.mu);
     for (const int fd : lpm_w) r.lpm_dev_dirty.insert(fd);

@@ -83,6 +83,8 @@ BPF_MAP_TYPE_PERCPU_ARRAY = 6
 BPF_MAP_TYPE_LRU_HASH = 9
 BPF_MAP_TYPE_LPM_TRIE = 11
 BPF_MAP_TYPE_RINGBUF = 27
+BPF_MAP_TYPE_QUEUE = 22
+BPF_MAP_TYPE_STACK = 23
 BPF_MAP_TYPE_BLOOM_FILTER = 30
 BPF_ANY, BPF_NOEXIST, BPF_EXIST = 0, 1, 2
 BPF_F_MMAPABLE = 1 << 10

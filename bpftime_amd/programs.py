@@ -753,3 +753,49 @@ def bloom_first_seen(fd: int) -> bytes:
     a.mov64(0, XDP_TX)
     a.label("out").exit()
     return a.assemble()
+
+
+# ---- BPF_MAP_TYPE_QUEUE / BPF_MAP_TYPE_STACK (bpf_map_push / pop_elem) ------
+_POP = 88
+
+
+def queue_sample(fd: int) -> bytes:
+    """Sampling to the host: for IPv4 frames push the record {u32 saddr, u32
+    packet length} (built on the stack) onto the queue and return the push's
+    result (0, or -1 as u32 when the queue is full); non-IPv4 and short frames
+    leave with XDP_PASS.  The host pops the records.  A parallel batch runs it
+    (add-only, flags 0).  fd: QUEUE (or STACK), value 8."""
+    a = Asm()
+    _ipv4_or_pass(a)
+    a.ldx(4, 4, 6, 26)                    # r4 = iph->saddr
+    a.stx(4, 10, -8, "r4")
+    a.alu64("sub", 3, "r6")               # r3 = data_end - data
+    a.stx(4, 10, -4, "r3")
+    a.ld_map_fd(1, fd).mov64(2, "r10").add64(2, -8).mov64(3, 0).call(_PUSH)
+    a.label("out").exit()
+    return a.assemble()
+
+
+def stack_take_id(fd: int, arr_fd: int) -> bytes:
+    """Free-list take: pop a u32 id from the stack and store it in the slot of
+    the ARRAY map that the packet names (the u32 at packet offset 0); XDP_DROP
+    when the stack is empty (or the slot does not exist), else XDP_PASS.  The
+    host fills the stack.  A parallel batch runs it (remove-only).
+    fd: STACK (or QUEUE), value 4; arr_fd: ARRAY key 4 value 4."""
+    a = Asm()
+    a.ldx(8, 6, 1, 0)                     # r6 = data
+    a.ld_map_fd(1, fd).mov64(2, "r10").add64(2, -4).call(_POP)
+    a.mov64(1, "r0")
+    a.mov64(0, XDP_DROP)
+    a.jmp("jne", 1, 0, "out")             # empty
+    a.ldx(4, 1, 6, 0)                     # the packet's index
+    a.stx(4, 10, -8, "r1")
+    a.ld_map_fd(1, arr_fd).mov64(2, "r10").add64(2, -8).call(BPF_FUNC_map_lookup_elem)
+    a.mov64(1, "r0")
+    a.mov64(0, XDP_DROP)
+    a.jmp("jeq", 1, 0, "out")
+    a.ldx(4, 2, 10, -4)                   # the id
+    a.stx(4, 1, 0, "r2")
+    a.mov64(0, XDP_PASS)
+    a.label("out").exit()
+    return a.assemble()

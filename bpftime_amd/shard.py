@@ -10,6 +10,9 @@ shards:
   * per-CPU maps       virtual-CPU slots are global ((unit // 64) % ncpu),
                        so per-slot deltas add up the same way
   * Bloom filters      bitwise OR of the shards' bit arrays (same seed)
+  * queues / stacks    add-only use (every shard only pushes): the initial
+                       elements, then each shard's appended elements in shard
+                       order; any other use is order dependent and is rejected
 The array rule runs in libbpftime_amd (bpftime_amd_merge_delta).
 """
 from __future__ import annotations
@@ -91,6 +94,28 @@ def merge_bloom(shards: List[np.ndarray]) -> np.ndarray:
             raise ValueError("shard size mismatch")
         acc |= s
     return acc
+
+
+def merge_queue_append(init: List[bytes], shards: List[List[bytes]], max_entries: int) -> List[bytes]:
+    """A QUEUE / STACK map's shards under add-only use, each given oldest
+    first (Map.queue_items): every shard must still begin with the initial
+    elements; the result is those, then what each shard appended, in shard
+    order -- the contents one map would hold had the shards' units run in
+    stream order, up to the order of pushes inside a shard.  A shard that
+    removed or evicted elements (it no longer begins with `init`) raises
+    ValueError: such a merge depends on the order of the shards' operations.
+    So does a result longer than max_entries, where the serial run's later
+    pushes would have failed."""
+    init = [bytes(e) for e in init]
+    out = list(init)
+    for g, sh in enumerate(shards):
+        sh = [bytes(e) for e in sh]
+        if sh[:len(init)] != init:
+            raise ValueError(f"shard {g} removed or replaced initial elements: only add-only shards merge")
+        out.extend(sh[len(init):])
+    if len(out) > max_entries:
+        raise ValueError(f"merged queue / stack has {len(out)} elements > max_entries {max_entries}")
+    return out
 
 
 def u64(b: bytes, i: int = 0) -> int:

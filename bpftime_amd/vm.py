@@ -182,7 +182,7 @@ class Map:
     def count(self) -> int:
         return lib().bpftime_amd_map_count(self.fd)
 
-    # BPF_MAP_TYPE_BLOOM_FILTER (bpftime_shm.cpp:168-200)
+    # BPF_MAP_TYPE_QUEUE / _STACK / _BLOOM_FILTER (bpftime_shm.cpp:168-200)
     def push(self, value: bytes, flags: int = 0) -> int:
         v = C.create_string_buffer(bytes(value), len(value))
         return lib().bpftime_map_push_elem(self.fd, v, flags)
@@ -195,6 +195,34 @@ class Map:
     def pop(self) -> int:
         v = C.create_string_buffer(max(self.value_size, 1))
         return lib().bpftime_map_pop_elem(self.fd, v)
+
+    def pop_value(self) -> Optional[bytes]:
+        """QUEUE / STACK: remove and return the oldest (queue) or newest
+        (stack) element; None when the map is empty (ENOENT)."""
+        v = C.create_string_buffer(max(self.value_size, 1))
+        if lib().bpftime_map_pop_elem(self.fd, v) != 0:
+            return None
+        return v.raw[:self.value_size]
+
+    def peek_value(self) -> Optional[bytes]:
+        """QUEUE / STACK: the element pop_value would return, left in place."""
+        v = C.create_string_buffer(max(self.value_size, 1))
+        if lib().bpftime_map_peek_elem(self.fd, v) != 0:
+            return None
+        return v.raw[:self.value_size]
+
+    def queue_items(self) -> list:
+        """QUEUE / STACK: the elements from the oldest to the newest, decoded
+        from a snapshot of the ring (128-byte header {u64 head, u64 tail}, then
+        max_entries slots; the element with ticket t in slot t % max_entries)."""
+        raw = self.snapshot()
+        head, tail = (int(x) for x in raw[:16].view(np.uint64))
+        stride = (self.value_size + 3) & ~3
+        out = []
+        for t in range(head, tail):
+            at = 128 + (t % self.max_entries) * stride
+            out.append(bytes(raw[at:at + self.value_size]))
+        return out
 
     def bloom_seed(self, set: Optional[int] = None) -> int:
         """The filter's jhash seed; `set` installs a new one first, which

@@ -56,16 +56,39 @@ struct bpf_link_create_args {
  * fix-size hash, map_handler.cpp:54-58), ARRAY (2), PROG_ARRAY (3, prog
  * fds, prog_array.cpp; the targets of bpf_tail_call, linked into the caller's
  * image at launch), PERCPU_HASH (5), PERCPU_ARRAY (6), LRU_HASH (9),
- * LPM_TRIE (11), RINGBUF (27), BLOOM_FILTER (30: key_size 0, nr_hashes =
- * map_extra & 0xF with 0 meaning 5, bloom_filter.cpp).  Returns fd or -1
- * (errno set). */
+ * LPM_TRIE (11), QUEUE (22) and STACK (23: value_size > 0 and max_entries >
+ * 0, the key size is not looked at; queue.cpp, stack.cpp), RINGBUF (27),
+ * BLOOM_FILTER (30: key_size 0, nr_hashes = map_extra & 0xF with 0 meaning 5,
+ * bloom_filter.cpp).  Returns fd or -1 (errno set). */
 int bpftime_maps_create(int fd, const char *name, struct bpf_map_attr attr);
 /* syscall-side ops (from_syscall = true), bpftime_shm.cpp:115-140 */
 const void *bpftime_map_lookup_elem(int fd, const void *key);
 long bpftime_map_update_elem(int fd, const void *key, const void *value, uint64_t flags);
 long bpftime_map_delete_elem(int fd, const void *key);
 int bpftime_map_get_next_key(int fd, const void *key, void *next_key);
-/* bpftime_shm.cpp:168-200.  A BLOOM_FILTER takes push (flags must be 0: sets
+/* bpftime_shm.cpp:168-200.  QUEUE / STACK: push appends (flags 0 / BPF_ANY or
+ * BPF_EXIST (2), anything else -1 with EINVAL; a full map gives -1 with E2BIG
+ * unless the flags are BPF_EXIST, which drops the oldest element -- the
+ * queue's head, the stack's bottom -- first); pop removes and copies out the
+ * oldest element (queue) or the newest (stack); peek copies without removing;
+ * an empty map gives -1 with ENOENT, a NULL value -1 with EINVAL.  On such a
+ * map update is a push with the key ignored and the flags not validated
+ * (only BPF_EXIST on a full map differs), lookup is a peek (a copy in the
+ * thread's lookup buffer), delete a pop that discards, get_next_key -1 with
+ * EINVAL.  The ring in device memory is the only copy: the host sees a
+ * finished batch's pushes and the next batch sees the host's.  Programs reach
+ * these maps through helpers 87 / 88 / 89 and 1 / 2 / 3.  In a parallel batch
+ * each QUEUE / STACK map must be add-only (helpers 87 / 2 with flags proven
+ * 0), remove-only (88 / 3) or peek-only (89 / 1); a program that mixes these
+ * on one map, pushes with non-zero or unproven flags, or reaches 87 / 88 / 89
+ * through a map register the loader cannot resolve runs only in
+ * EBPF_BATCH_ORDERED batches, which give the reference's sequence exactly;
+ * other batches of it are refused at launch.  Across streams a launch that
+ * removes from or peeks such a map never overlaps one that adds to one, and
+ * an ORDERED launch that touches one (ebpf_exec included) overlaps no other
+ * launch that touches one: whichever comes second synchronises the device
+ * first.
+ * A BLOOM_FILTER takes push (flags must be 0: sets
  * the value's bits, returns 0) and peek (0 when every bit of the value is
  * set, else -1 with ENOENT; *value is not written); pop gives -1 with
  * EOPNOTSUPP.  Every other map type: -ENOTSUP.  lookup / delete /
@@ -184,7 +207,11 @@ int bpftime_amd_map_restore(int fd, const void *in, uint64_t bytes);
 /* hash maps: bucket count and device slot geometry */
 int bpftime_amd_map_geometry(int fd, uint64_t *nbuckets, uint32_t *slot_size, uint32_t *key_off,
                              uint32_t *val_off, uint32_t *ncpu);
+/* (a QUEUE / STACK map: tail - head) */
 uint64_t bpftime_amd_map_count(int fd);
+/* 1 when this build has a map family for the BPF_MAP_TYPE_* number, else 0
+ * (needs no device) */
+int bpftime_amd_map_type_supported(uint32_t type);
 /* BLOOM_FILTER: the jhash seed (drawn at random per map, as the reference
  * draws it) to *out; a non-NULL `set` installs *set first and zeroes the bit
  * array -- bits set under another seed mean nothing.  0, or -1 (not a Bloom

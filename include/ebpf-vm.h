@@ -93,7 +93,11 @@ ebpf_jit_fn ebpf_load_aot_object(struct ebpf_vm *vm, const void *buf, size_t buf
 #define EBPF_CTX_SYSCALL_EXIT 3
 
 #define EBPF_BATCH_SYNC 0x1    /* wait for completion; return the failed-unit count */
-#define EBPF_BATCH_ORDERED 0x2 /* one lane, units in index order (exact sequential semantics) */
+/* one lane, units in index order (exact sequential semantics).  The only batches that run a
+ * program which mixes adding to, removing from and peeking one QUEUE / STACK map, pushes with
+ * non-zero or unproven flags (BPF_EXIST), or writes an LPM trie: other batches of it are refused
+ * at launch (bpftime_amd.h, bpftime_map_push_elem) */
+#define EBPF_BATCH_ORDERED 0x2
 #define EBPF_BATCH_UNCHECKED 0x4 /* skip the global-window confinement check */
 #define EBPF_BATCH_SYS_NR 0x8    /* EBPF_CTX_SYSCALL: only records whose id == sys_nr run (per-syscall attach) */
 #define EBPF_BATCH_TIMED 0x10    /* record events around the batch's kernels (bpftime_amd_last_batch_ms) */
