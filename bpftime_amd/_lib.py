@@ -53,6 +53,15 @@ class PerfEvent(C.Structure):
                 ("module_name", C.c_char_p), ("cpu", C.c_int), ("sample_type", C.c_int32), ("config", C.c_int64)]
 
 
+class LaunchInfo(C.Structure):
+    """struct bpftime_amd_launch_info (include/bpftime_amd.h)"""
+    _fields_ = [("units", C.c_uint64), ("grid", C.c_uint32), ("block", C.c_uint32), ("comb_entries", C.c_uint32),
+                ("lcache_sets", C.c_uint32), ("stage", C.c_uint32), ("gregs", C.c_uint32), ("gctx", C.c_uint32),
+                ("miss_cap", C.c_uint32), ("tail_lds_depths", C.c_uint32), ("tail_lds_words", C.c_uint32),
+                ("occupancy", C.c_int32), ("flush_log", C.c_uint32), ("miss_log", C.c_uint32),
+                ("ordered", C.c_uint32)]
+
+
 # (name, restype, argtypes) for every exported symbol of include/*.h
 SIGNATURES = [
     # include/ebpf-vm.h
@@ -112,6 +121,7 @@ SIGNATURES = [
     ("bpftime_amd_vm_fast_handler", C.c_char_p, [C.c_void_p, C.c_uint32, C.c_uint32]),
     ("bpftime_amd_vm_counter_info", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32),
                                               C.POINTER(C.c_uint32)]),
+    ("bpftime_amd_vm_last_launch", C.c_int, [C.c_void_p, C.POINTER(LaunchInfo)]),
     ("bpftime_import_global_shm_from_json", C.c_int, [C.c_char_p]),
     ("bpftime_export_global_shm_to_json", C.c_int, [C.c_char_p]),
     ("bpftime_import_shm_handler_from_json", C.c_int, [C.c_int, C.c_char_p]),

@@ -357,6 +357,9 @@ class Mi355xVm {
   StreamBufs logs, frames, scratch, regs, misses;
   // the kernels of the last EBPF_BATCH_TIMED batch
   hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
+  // the plan of the last launch (bpftime_amd_vm_last_launch; block 0: none yet)
+  std::mutex last_mu;
+  bpftime_amd_launch_info last{};
 
   Mi355xVm() {
     // bpftime_prog.cpp:126-127 defaults, pointed at the device registry
@@ -1119,6 +1122,24 @@ int Mi355xVm::exec_batch(const ebpf_batch *b) {
             "miss cap %u tail lds %u x %u words occ %d\n",
             (unsigned long long)b->count, grid, block, p.comb_entries, p.lcache, p.stage, (unsigned)prog.stack_size,
             p.gregs ? 1 : 0, p.gctx ? 1 : 0, p.unwind_idx, p.miss_cap, p.tail_lds & 0xff, p.tail_lds >> 8, occ_fit);
+  {
+    std::lock_guard<std::mutex> g(last_mu);
+    last.units = b->count;
+    last.grid = grid;
+    last.block = block;
+    last.comb_entries = p.comb_entries;
+    last.lcache_sets = p.lcache;
+    last.stage = p.stage;
+    last.gregs = p.gregs ? 1 : 0;
+    last.gctx = p.gctx ? 1 : 0;
+    last.miss_cap = p.miss_cap;
+    last.tail_lds_depths = p.tail_lds & 0xff;
+    last.tail_lds_words = p.tail_lds >> 8;
+    last.occupancy = occ_fit;
+    last.flush_log = p.flush_log ? 1 : 0;
+    last.miss_log = p.miss_log ? 1 : 0;
+    last.ordered = ordered ? 1 : 0;
+  }
   // EBPF_BATCH_TIMED: events around this batch's kernels only (the host
   // work above -- linking, buffers, index upkeep -- stays outside)
   const bool timed = (b->flags & EBPF_BATCH_TIMED) != 0;
@@ -1623,6 +1644,14 @@ int bpftime_amd_vm_counter_info(const struct ebpf_vm *vm, uint32_t ctx_kind, uin
     if (f.add_site[i]) ((f.fast[i].w1 & FW_NODEFER) ? nn : nd)++;
   if (deferred) *deferred = nd;
   if (direct) *direct = nn;
+  return 0;
+}
+
+int bpftime_amd_vm_last_launch(const struct ebpf_vm *vm, struct bpftime_amd_launch_info *out) {
+  if (!vm || !out) return -1;
+  std::lock_guard<std::mutex> g(vm->impl->last_mu);
+  if (!vm->impl->last.block) return -1;
+  *out = vm->impl->last;
   return 0;
 }
 

@@ -14,7 +14,7 @@ from typing import Optional
 import numpy as np
 
 from . import isa
-from ._lib import BpfLinkCreateArgs, BpfMapAttr, EbpfBatch, SysRecords, lib
+from ._lib import BpfLinkCreateArgs, BpfMapAttr, EbpfBatch, LaunchInfo, SysRecords, lib
 
 CTX_RAW, CTX_XDP, CTX_SYSCALL, CTX_SYSCALL_EXIT = 0, 1, 2, 3
 SYSCALL_RECORD, SYSCALL_RECORD_FULL, SYSCALL_RECORD_TIMED = 64, 96, 128  # include/bpftime_amd.h replay records
@@ -322,6 +322,19 @@ class VM:
         if lib().bpftime_amd_vm_counter_info(C.c_void_p(self.h), kind, C.byref(d), C.byref(n)):
             raise EbpfError("vm_counter_info failed")
         return d.value, n.value
+
+    def last_launch(self) -> dict:
+        """The plan of this VM's last batch launch (struct
+        bpftime_amd_launch_info): units, grid, block, comb_entries,
+        lcache_sets, stage, miss_cap, tail_lds_depths, tail_lds_words,
+        occupancy, and gregs, gctx, flush_log, miss_log, ordered as bools."""
+        li = LaunchInfo()
+        if lib().bpftime_amd_vm_last_launch(C.c_void_p(self.h), C.byref(li)):
+            raise EbpfError("no batch launched yet")
+        d = {name: getattr(li, name) for name, _ in LaunchInfo._fields_}
+        for k in ("gregs", "gctx", "flush_log", "miss_log", "ordered"):
+            d[k] = bool(d[k])
+        return d
 
     def set_step_limit(self, n: int) -> None:
         lib().bpftime_amd_set_step_limit(C.c_void_p(self.h), n)

@@ -252,6 +252,25 @@ const char *bpftime_amd_vm_fast_handler(const struct ebpf_vm *vm, uint32_t ctx_k
  * summed per wave / block before they reach memory (nothing the unit runs
  * afterwards can observe them), `direct` reach memory at once. */
 int bpftime_amd_vm_counter_info(const struct ebpf_vm *vm, uint32_t ctx_kind, uint32_t *deferred, uint32_t *direct);
+/* The plan of the vm's last batch launch, as exec_batch chose it (what the
+ * BPFTIME_AMD_VERBOSE line prints): read-only, for tests and tools that must
+ * know which of the interchangeable mechanisms a launch ran on. */
+struct bpftime_amd_launch_info {
+  uint64_t units;         /* b->count */
+  uint32_t grid, block;   /* blocks, lanes per block (256 or 1024) */
+  uint32_t comb_entries;  /* the block's combining table (0: none) */
+  uint32_t lcache_sets;   /* the block's lookup cache (0: none) */
+  uint32_t stage;         /* bytes of each unit staged in LDS (0: unstaged) */
+  uint32_t gregs, gctx;   /* register copy / XDP ctx in global memory (else LDS) */
+  uint32_t miss_cap;      /* records per block and partition of the miss log */
+  uint32_t tail_lds_depths, tail_lds_words; /* tail-call frames kept in LDS */
+  int32_t occupancy;      /* resident blocks per CU */
+  uint32_t flush_log;     /* block-end flushes go through the log and k_comb_merge */
+  uint32_t miss_log;      /* table misses go through the log and k_miss_merge */
+  uint32_t ordered;       /* EBPF_BATCH_ORDERED: one lane, adds straight to memory */
+};
+/* 0, or -1 when the vm has launched no batch yet. */
+int bpftime_amd_vm_last_launch(const struct ebpf_vm *vm, struct bpftime_amd_launch_info *out);
 
 /* ---- handler JSON (csrc/shm_json.cpp) ----
  * The reference's shm export / import format (runtime/include/bpftime_shm.hpp:

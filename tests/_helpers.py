@@ -4,7 +4,8 @@ import struct
 
 import numpy as np
 
-from bpftime_amd import isa
+from bpftime_amd import gen, isa
+from bpftime_amd.isa import Asm
 
 
 def make_maps(specs, po=None, dev=None):
@@ -32,3 +33,32 @@ def xdp_counter_maps(po, dev, ctl_flag=0):
 
 def u64s(b):
     return np.frombuffer(b, dtype=np.uint64)
+
+
+def update_existing_prog(fd):
+    """-> (code, pc of the update call).  bpf_map_update_elem of a HASH map
+    (u32 key, 16-byte value) with key and value on the stack: the unit's word
+    0 is the key, its bytes 8..23 the value; then a lookup of the key; r0 =
+    the value's second word + the update's return, 99 on a miss."""
+    a = Asm()
+    a.ldx(4, 2, 1, 0).stx(4, 10, -4, "r2")                 # key = unit word 0
+    a.ldx(8, 3, 1, 8).stx(8, 10, -24, "r3")                # value = unit bytes 8..23
+    a.ldx(8, 3, 1, 16).stx(8, 10, -16, "r3")
+    a.ld_map_fd(1, fd).mov64(2, "r10").add64(2, -4).mov64(3, "r10").add64(3, -24).mov64(4, 0)
+    at = a.pc
+    a.call(isa.BPF_FUNC_map_update_elem)
+    a.mov64(6, "r0")
+    a.ld_map_fd(1, fd).mov64(2, "r10").add64(2, -4).call(isa.BPF_FUNC_map_lookup_elem)
+    a.jmp("jeq", 0, 0, "miss")
+    a.ldx(8, 0, 0, 8).alu64("add", 0, "r6").exit()
+    a.label("miss").mov64(0, 99).exit()
+    return a.assemble(), at
+
+
+def update_existing_units(n):
+    """32-byte units for update_existing_prog: key = the unit's index."""
+    units = np.zeros((n, 32), dtype=np.uint8)
+    units.view(np.uint32)[:, 0] = np.arange(n, dtype=np.uint32)
+    units.view(np.uint64)[:, 1] = gen.sm64(11, np.arange(n, dtype=np.uint64))
+    units.view(np.uint64)[:, 2] = gen.sm64(12, np.arange(n, dtype=np.uint64))
+    return units

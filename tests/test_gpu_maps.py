@@ -12,7 +12,7 @@ from bpftime_amd import gen, isa, programs
 from bpftime_amd.isa import (Asm, ATOMIC_ADD, BPF_FUNC_map_lookup_elem, BPF_FUNC_map_update_elem,
                              BPF_NOEXIST)
 
-from _helpers import make_maps
+from _helpers import make_maps, update_existing_prog, update_existing_units
 
 pytestmark = pytest.mark.gpu
 
@@ -554,23 +554,8 @@ def test_hash_update_existing_keys_in_asm(fresh_oracle, fresh_runtime, present):
     for k in range(int(n * present)):
         key, val = struct.pack("<I", k), struct.pack("<QQ", 7 * k, k)
         assert om.update(key, val) == 0 and dm.update(key, val) == 0
-    a = Asm()
-    a.ldx(4, 2, 1, 0).stx(4, 10, -4, "r2")                 # key = unit word 0
-    a.ldx(8, 3, 1, 8).stx(8, 10, -24, "r3")                # value = unit bytes 8..23
-    a.ldx(8, 3, 1, 16).stx(8, 10, -16, "r3")
-    a.ld_map_fd(1, dm.fd).mov64(2, "r10").add64(2, -4).mov64(3, "r10").add64(3, -24).mov64(4, 0)
-    a.call(isa.BPF_FUNC_map_update_elem)
-    a.mov64(6, "r0")
-    a.ld_map_fd(1, dm.fd).mov64(2, "r10").add64(2, -4).call(isa.BPF_FUNC_map_lookup_elem)
-    a.jmp("jeq", 0, 0, "miss")
-    a.ldx(8, 0, 0, 8).alu64("add", 0, "r6").exit()
-    a.label("miss").mov64(0, 99).exit()
-    code = a.assemble()
-    units = np.zeros((n, 32), dtype=np.uint8)
-    w = units.view(np.uint32)
-    w[:, 0] = np.arange(n, dtype=np.uint32)
-    units.view(np.uint64)[:, 1] = gen.sm64(11, np.arange(n, dtype=np.uint64))
-    units.view(np.uint64)[:, 2] = gen.sm64(12, np.arange(n, dtype=np.uint64))
+    code, _ = update_existing_prog(dm.fd)
+    units = update_existing_units(n)
     ovm = po.OracleVM()
     ovm.load(code)
     orets = ovm.run_raw(units.copy(), 32)
