@@ -3,23 +3,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "common.hpp"
+#include "mem_guard.hpp"  // is_lds_addr, is_scratch_addr, Win, the range guard
 
 namespace bpftime_amd {
-
-__device__ __forceinline__ bool is_lds_addr(uint64_t a) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __builtin_amdgcn_is_shared((const void *)a);
-#else
-  return false;
-#endif
-}
-__device__ __forceinline__ bool is_scratch_addr(uint64_t a) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __builtin_amdgcn_is_private((const void *)a);
-#else
-  return false;
-#endif
-}
 
 typedef uint16_t u16u __attribute__((aligned(1)));
 typedef uint32_t u32u __attribute__((aligned(1)));
@@ -43,21 +29,6 @@ __device__ __forceinline__ void mem_store(uint64_t a, uint32_t sz, uint64_t v) {
     default: *(u64u *)a = v; break;
   }
 }
-
-// Global windows a program may access: the batch, the map arena, and the
-// lanes' scratch words (PROG_ARRAY lookup copies; C++ tier only -- the asm
-// window check leaves those accesses to it).
-struct Win {
-  uint64_t lo1, hi1, lo2, hi2, lo3, hi3;
-  bool checked;
-  __device__ __forceinline__ bool ok(uint64_t a, uint32_t sz) const {
-    if (!checked) return true;
-    if (is_lds_addr(a) || is_scratch_addr(a)) return true;
-    uint64_t e = a + sz;
-    return (a >= lo1 && e <= hi1 && e >= a) || (a >= lo2 && e <= hi2 && e >= a) ||
-           (a >= lo3 && e <= hi3 && e >= a);
-  }
-};
 
 // ---------------------------------------------------------------------------
 // Device maps (helpers 1/2/3).  Semantics follow the reference helper view:
@@ -1413,6 +1384,106 @@ __device__ __noinline__ uint64_t helper_qs(const DMap *maps, uint64_t fd, uint64
     done |= __ballot(fd == f0);
   }
   return out;
+}
+
+// ---------------------------------------------------------------------------
+// bpf_probe_read / _user / _kernel (4 / 112 / 113), bpf_probe_read_str /
+// _user_str / _kernel_str (45 / 114 / 115) and bpf_strncmp (182):
+// bpf_helper.cpp:153-209, :431-437, :78-81.  Every byte these helpers touch
+// is inside a range mem_guard.hpp accepted first; a rejected range answers
+// -EFAULT with the destination untouched.  All loops are per lane: no lane
+// waits on another.
+// ---------------------------------------------------------------------------
+constexpr uint64_t kEfault = (uint64_t)(int64_t)-14;
+
+__device__ __forceinline__ uint8_t mem_ld8(uint64_t a) { return *(const volatile uint8_t *)a; }
+__device__ __forceinline__ void mem_st8(uint64_t a, uint8_t v) { *(volatile uint8_t *)a = v; }
+
+// Copy n bytes between flat addresses of any alignment (scratch stack, LDS
+// ctx, packet, map arena).  Contract: where the ranges overlap (|d - s| < n)
+// the bytes are copied one at a time in ascending order, so a destination
+// that starts inside the source repeats the bytes in front of it.  Disjoint
+// ranges move naturally aligned 8-byte words when d and s are congruent
+// modulo 8, 4-byte words when congruent modulo 4 (byte head and tail), and
+// otherwise aligned 4-byte word loads of the source with byte extraction
+// (the pattern of key_eq).  No access leaves [s, s + n) or [d, d + n).
+__device__ __forceinline__ void mem_copy(uint64_t d, uint64_t s, uint64_t n) {
+  uint64_t i = 0;
+  if (d - s < n || s - d < n) {
+    for (; i < n; i++) mem_st8(d + i, mem_ld8(s + i));
+    return;
+  }
+  const uint32_t x = (uint32_t)(d ^ s);
+  if ((x & 7) == 0) {
+    for (; i < n && ((s + i) & 7); i++) mem_st8(d + i, mem_ld8(s + i));
+    for (; i + 8 <= n; i += 8) *(volatile uint64_t *)(d + i) = *(const volatile uint64_t *)(s + i);
+  } else if ((x & 3) == 0) {
+    for (; i < n && ((s + i) & 3); i++) mem_st8(d + i, mem_ld8(s + i));
+    for (; i + 4 <= n; i += 4) *(volatile uint32_t *)(d + i) = *(const volatile uint32_t *)(s + i);
+  } else {
+    for (; i < n && ((s + i) & 3); i++) mem_st8(d + i, mem_ld8(s + i));
+    for (; i + 4 <= n; i += 4) {
+      const uint32_t w = *(const volatile uint32_t *)(s + i);
+      mem_st8(d + i, (uint8_t)w);
+      mem_st8(d + i + 1, (uint8_t)(w >> 8));
+      mem_st8(d + i + 2, (uint8_t)(w >> 16));
+      mem_st8(d + i + 3, (uint8_t)(w >> 24));
+    }
+  }
+  for (; i < n; i++) mem_st8(d + i, mem_ld8(s + i));
+}
+
+__device__ __forceinline__ void mem_zero(uint64_t d, uint64_t n) {
+  uint64_t i = 0;
+  for (; i < n && ((d + i) & 7); i++) mem_st8(d + i, 0);
+  for (; i + 8 <= n; i += 8) *(volatile uint64_t *)(d + i) = 0;
+  for (; i < n; i++) mem_st8(d + i, 0);
+}
+
+// The one entry of the seven helpers (interp.hip call_helper; the id is
+// wave-uniform, pointers and sizes are per lane).
+//   probe_read*(dst, size, src): size < 0 -EFAULT, 0 -> 0, else a copy.
+//   probe_read*_str(buf, bufsz, src): strncpy -- the source up to and with
+//     its first NUL, or bufsz bytes when it has none, the rest of buf zeroed;
+//     returns 0 (the reference's answer, not the kernel's length).  The
+//     length is found first, bounded by the room of the region the source
+//     starts in, so no byte after the NUL or past the region is read; then
+//     the copy.
+//   strncmp(s1, s1_sz, s2): 0, or the difference of the first differing
+//     bytes as unsigned chars.
+__device__ __noinline__ uint64_t helper_mem(uint32_t id, uint64_t a1, uint64_t a2, uint64_t a3, Win win,
+                                            MemLane ml) {
+  if (id == 182) {
+    if (a2 == 0) return 0;
+    const uint64_t r1 = mem_room(win, ml, a1), r2 = mem_room(win, ml, a3);
+    uint64_t lim = r1 < r2 ? r1 : r2;
+    if (lim == 0) return kEfault;
+    if (lim > a2) lim = a2;
+    for (uint64_t i = 0; i < lim; i++) {
+      const uint8_t c1 = mem_ld8(a1 + i), c2 = mem_ld8(a3 + i);
+      if (c1 != c2) return (uint64_t)(int64_t)((int32_t)c1 - (int32_t)c2);
+      if (c1 == 0) return 0;
+    }
+    return lim < a2 ? kEfault : 0;  // a region ended before the strings did
+  }
+  if (id == 45 || id == 114 || id == 115) {
+    if (a2 == 0) return 0;
+    if (!mem_range_ok(win, ml, a1, a2)) return kEfault;
+    const uint64_t room = mem_room(win, ml, a3);
+    const uint64_t lim = room < a2 ? room : a2;
+    uint64_t len = 0;
+    while (len < lim && mem_ld8(a3 + len) != 0) len++;
+    if (len == lim && lim < a2) return kEfault;  // (room 0 too: no byte accepted)
+    mem_copy(a1, a3, len);
+    mem_zero(a1 + len, a2 - len);
+    return 0;
+  }
+  // 4 / 112 / 113: one function, as in the reference
+  if ((int64_t)a2 < 0) return kEfault;
+  if (a2 == 0) return 0;
+  if (!mem_range_ok(win, ml, a1, a2) || !mem_range_ok(win, ml, a3, a2)) return kEfault;
+  mem_copy(a1, a3, a2);
+  return 0;
 }
 
 __device__ uint64_t helper_lookup(const DMap *maps, uint64_t fd, uint64_t key, LaneEnv &env) {

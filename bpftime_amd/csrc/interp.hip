@@ -46,8 +46,13 @@ namespace bpftime_amd {
 template <bool BLOOM>
 __device__ __forceinline__ uint64_t call_helper(uint32_t id, uint64_t a1, uint64_t a2, uint64_t a3, uint64_t a4,
                                                 uint64_t a5, const DMap *maps, uint32_t ncpu, uint64_t seed,
-                                                LaneEnv &env, uint32_t *err) {
+                                                LaneEnv &env, uint32_t *err, const Win &win, const MemLane &ml) {
   if constexpr (BLOOM) {
+    // bpf_probe_read* / bpf_probe_read_*_str / bpf_strncmp: byte ranges of
+    // run-time length, checked against the windows and the lane's own stack
+    // and ctx extents -- dev_helpers.hpp helper_mem
+    if (id == 4 || id == 112 || id == 113 || id == 45 || id == 114 || id == 115 || id == 182)
+      return helper_mem(id, a1, a2, a3, win, ml);
     // a QUEUE / STACK map: push / pop / peek, and lookup (a peek that returns
     // the slot), update (a push, the key ignored) and delete (a pop that
     // discards) -- dev_helpers.hpp helper_qs
@@ -1145,9 +1150,13 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(4))) void k_
         env.ktime = p.kt_base ? *(const uint64_t *)(p.kt_base + unit * p.kt_stride) : 0;
         uint32_t cerr = E_OK;
         uint64_t *R = c.R;
+        // the lane's own memory for helper_mem (scratch-stack instances only:
+        // its stack, and the XDP ctx copy -- other kinds' ctx is the unit)
+        const MemLane ml{stack_top - kStackSize, KIND == CTX_XDP ? (uint64_t)(uintptr_t)my_ctx : 0, kStackSize,
+                         KIND == CTX_XDP ? kXdpCtxBytes : 0u};
         const uint64_t rv = call_helper<BIGSTACK>(c.call_id, R[1 * kBlock], R[2 * kBlock], R[3 * kBlock], R[4 * kBlock],
                                         R[5 * kBlock], p.maps, p.ncpu,
-                                        (p.first_unit + unit) ^ ((uint64_t)c.steps << 40), env, &cerr);
+                                        (p.first_unit + unit) ^ ((uint64_t)c.steps << 40), env, &cerr, c.win, ml);
         R[0] = rv;
         miss_fd = env.miss_fd;
         miss_hash = env.miss_hash;
@@ -1627,10 +1636,14 @@ __global__ __launch_bounds__(kBlock) void k_sys_seq(SeqParams p) {
           uint32_t cerr = E_OK;
           uint64_t *R = c.R;
           const uint32_t cid = __builtin_amdgcn_readfirstlane(c.call_id);
+          // the lane's own memory for helper_mem: its stack (LDS or private)
+          // and the callback's ctx copy, {id, args} or {id, ret}
+          const uint32_t sbytes = fast ? kLdsStackMax : kStackSize;
+          const MemLane ml{stack_top - sbytes, (uint64_t)(uintptr_t)ctx, sbytes, enter ? 64u : 24u};
           const uint64_t rv = cid == kTailHelper ? 0
                               : call_helper<true>(cid, R[1 * kBlock], R[2 * kBlock], R[3 * kBlock], R[4 * kBlock],
                                             R[5 * kBlock], p.maps, p.ncpu, idx ^ ((uint64_t)c.steps << 40), env,
-                                            &cerr);
+                                            &cerr, c.win, ml);
           if (cid == kTailHelper) cerr = E_BADOP;  // (the host refuses such programs)
           R[0] = rv;
           miss_fd = env.miss_fd;

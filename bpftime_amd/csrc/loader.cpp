@@ -27,11 +27,23 @@ bool device_helper_supported(uint32_t id) {
     case 58: case 187:  // bpf_override_return / bpf_set_retval (syscall dispatch state)
     case 14:            // bpf_get_current_pid_tgid (recorded caller / launching thread)
     case 87: case 88: case 89:  // bpf_map_push / pop / peek_elem (QUEUE, STACK, BLOOM_FILTER)
+    case 4: case 112: case 113:   // bpf_probe_read / _user / _kernel
+    case 45: case 114: case 115:  // bpf_probe_read_str / _user_str / _kernel_str
+    case 182:                     // bpf_strncmp
     case kTailHelper:
       return true;
   }
   return false;
 }
+
+// The helpers that copy (or compare) byte ranges of run-time length
+// (dev_helpers.hpp helper_mem): probe_read*(dst, size, src) and
+// probe_read*_str(buf, bufsz, src) write r1's range and read r3's;
+// strncmp(s1, s1_sz, s2) reads both.
+static bool mem_copy_helper(int64_t id) {
+  return id == 4 || id == 112 || id == 113 || id == 45 || id == 114 || id == 115;
+}
+static bool mem_helper(int64_t id) { return mem_copy_helper(id) || id == 182; }
 
 static std::string fmt(const char *f, ...) __attribute__((format(printf, 1, 2)));
 static std::string fmt(const char *f, ...) {
@@ -235,6 +247,8 @@ static int helper_arity(uint32_t id) {
     case 1: case 3: case 44: case 65: return 2;  // map_lookup/delete_elem, xdp_adjust_head/tail
     case 88: case 89: return 2;                // map_pop/peek_elem(map, value)
     case 87: return 3;                         // map_push_elem(map, value, flags)
+    case 4: case 112: case 113: case 45: case 114: case 115: case 182:
+      return 3;                                // probe_read*(dst, size, src), strncmp(s1, s1_sz, s2)
     case 2: case 189: return 4;                // map_update_elem, xdp_load_bytes
     case kTailHelper: return 3;                // tail_call(ctx, prog_array, index)
     case (uint32_t)kRetHelper: return 0;       // a linked tail-call target's exit
@@ -485,6 +499,7 @@ int load_program(const RawInsn *code, size_t n, const std::map<size_t, size_t> &
       }
       if (cur.imm == 3) out.may_delete = true;
       if (cur.imm == 87 || cur.imm == 88 || cur.imm == 89) out.bloom = true;
+      if (mem_helper(cur.imm)) out.bloom = true;  // (helper_mem: the scratch-stack kernels' too)
       if (cur.imm == 58 || cur.imm == 187) out.sets_retval = true;
     } else if (cur.code == 0x18) {
       if (i + 1 == n) {
@@ -888,6 +903,9 @@ static bool pointer_kinds(const std::vector<DInsn> &p, const std::vector<uint8_t
       case X_CALL: {
         // r1-r5 survive (ubpf); a lookup on a bound map yields a nullable value pointer
         const PVal m = st[1];
+        // (a copy helper's destination of run-time length inside the ctx may
+        // reach its packet pointers)
+        if (mem_copy_helper(d.hi) && st[1].kind == P_CTX) ctx_written = true;
         // (not of a QUEUE / STACK: the slot a peek returns is no element of a keyed value array)
         st[0] = (d.hi == 1 && m.kind == P_MAPFD && map_rec(m.id) && !qs_type(map_rec(m.id)->type))
                     ? PVal{P_MVNULL, 0, m.id}
@@ -1027,6 +1045,10 @@ static void accesses(const std::vector<DInsn> &p, uint32_t i, const std::vector<
     case 130: arg(2); return;
     case 132: case 133: arg(1); return;
     case 189: arg(3); return;
+    // probe_read* / probe_read*_str write r1's range and read r3's; strncmp
+    // reads both: a map-value or unplaced pointer is an access of that map's
+    // (of any map's) values, which a deferred counter add must not precede
+    case 4: case 112: case 113: case 45: case 114: case 115: case 182: arg(1); arg(3); return;
     default:
       if ((int32_t)id == kRetHelper) return;
       out.push_back(Loc{Loc::ANY, -1, 0, 0});  // tail calls and anything else
@@ -1124,6 +1146,11 @@ static void const_loads(const std::vector<DInsn> &p, const std::vector<uint8_t> 
             break;
           case 189:
             writes.push_back(loc_of(p, st[3], 0, kUnknownLen));
+            break;
+          case 4: case 112: case 113: case 45: case 114: case 115:  // probe_read*(dst, ...) write *dst
+            writes.push_back(loc_of(p, st[1], 0, kUnknownLen));
+            break;
+          case 182:  // strncmp: reads only
             break;
           default:
             if (d.hi != kRetHelper) writes.push_back(Loc{Loc::ANY, -1, 0, 0});
@@ -1368,6 +1395,10 @@ static void tail_save_masks(const std::vector<DInsn> &p, const std::vector<std::
       case 88: case 89: write(st[2], 0, 1 << 16); break;  // pop / peek of a QUEUE / STACK write *value
       case 44: case 65: ctx_bytes(0, 16); break;  // adjust_head / adjust_tail: data, data_end
       case 189: write(st[3], 0, 1 << 16); break;  // xdp_load_bytes(ctx, off, to, len)
+      case 4: case 112: case 113: case 45: case 114: case 115:
+        write(st[1], 0, 1 << 16);  // probe_read*(dst, size, src) write *dst
+        break;
+      case 182: break;  // strncmp: reads only
       default:
         if (d.hi != kRetHelper) {
           cm = 0x3f;
@@ -1465,6 +1496,15 @@ static void map_effects(const std::vector<DInsn> &prog, const std::vector<std::v
           case 2: case 3: case 130: case 131: case 87: case 88: mark(fd, FX_WRITE); break;  // update, delete, ringbuf output / reserve, push, pop
           case 5: case 7: case 8: case 14: case 28: case 44: case 58: case 65: case 132: case 133: case 187: case 189:
             break;  // no map effects (132 / 133 finish a reservation 131 marked)
+          case 4: case 112: case 113: case 45: case 114: case 115: case 182: {
+            // probe_read* / probe_read*_str write through r1 and read through
+            // r3, strncmp reads through both: map effects when the pointer
+            // is a map value's (or cannot be placed: any map)
+            const int32_t t1 = target(i, st[1], 0, 1), t3 = target(i, st[3], 0, 1);
+            if (t1 != -2) mark(t1, d.hi == 182 ? FX_READ : FX_WRITE);
+            if (t3 != -2) mark(t3, FX_READ);
+            break;
+          }
           default: mark(-1, FX_READ | FX_WRITE); break;                 // bpf_tail_call, anything else
         }
         break;
@@ -1540,8 +1580,9 @@ void build_fast(const LoadOut &lo, bool xdp, FastForm &out) {
   if (kinds_ok) map_effects(prog, in, out);  // (else any_fx stays: every map, read and written)
   for (size_t i = 0; kinds_ok && i < prog.size(); i++) {
     const DInsn &d = prog[i];
-    if (d.op != X_ST && d.op != X_STX && d.op != X_RMW_ADD && d.op != X_ATOMIC) continue;
-    const uint8_t k = in[i][d.dst].kind;
+    const bool copies = d.op == X_CALL && mem_copy_helper(d.hi);  // (writes through r1)
+    if (d.op != X_ST && d.op != X_STX && d.op != X_RMW_ADD && d.op != X_ATOMIC && !copies) continue;
+    const uint8_t k = in[i][copies ? 1 : d.dst].kind;
     if (k != P_UNDEF && k != P_STK && k != P_MAPVAL && k != P_CONST) out.stores_unit = true;
   }
   if (!kinds_ok) {

@@ -1584,7 +1584,10 @@ int bpftime_amd_register_default_helpers(struct ebpf_vm *vm) {
            {1, "bpf_map_lookup_elem"},       {2, "bpf_map_update_elem"}, {3, "bpf_map_delete_elem"},
            {58, "bpf_override_return"},      {187, "bpf_set_retval"},
            {14, "bpf_get_current_pid_tgid"},
-           {87, "bpf_map_push_elem"},        {88, "bpf_map_pop_elem"},   {89, "bpf_map_peek_elem"}};
+           {87, "bpf_map_push_elem"},        {88, "bpf_map_pop_elem"},   {89, "bpf_map_peek_elem"},
+           {4, "bpf_probe_read"},            {112, "bpf_probe_read_user"}, {113, "bpf_probe_read_kernel"},
+           {45, "bpf_probe_read_str"},       {114, "bpf_probe_read_user_str"},
+           {115, "bpf_probe_read_kernel_str"}, {182, "bpf_strncmp"}};
   int err = 0;
   for (auto &e : h) err |= ebpf_register(vm, e.id, e.name, nullptr);
   return err ? -1 : 0;

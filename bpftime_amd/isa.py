@@ -54,6 +54,7 @@ XDP_ABORTED, XDP_DROP, XDP_PASS, XDP_TX, XDP_REDIRECT = range(5)
 BPF_FUNC_map_lookup_elem = 1
 BPF_FUNC_map_update_elem = 2
 BPF_FUNC_map_delete_elem = 3
+BPF_FUNC_probe_read = 4
 BPF_FUNC_ktime_get_ns = 5
 BPF_FUNC_trace_printk = 6
 BPF_FUNC_get_prandom_u32 = 7
@@ -73,6 +74,12 @@ BPF_FUNC_ringbuf_reserve = 131
 BPF_FUNC_ringbuf_submit = 132
 BPF_FUNC_ringbuf_discard = 133
 BPF_FUNC_xdp_load_bytes = 189
+BPF_FUNC_probe_read_str = 45
+BPF_FUNC_probe_read_user = 112
+BPF_FUNC_probe_read_kernel = 113
+BPF_FUNC_probe_read_user_str = 114
+BPF_FUNC_probe_read_kernel_str = 115
+BPF_FUNC_strncmp = 182
 
 # map types (linux/bpf.h)
 BPF_MAP_TYPE_HASH = 1

@@ -799,3 +799,32 @@ def stack_take_id(fd: int, arr_fd: int) -> bytes:
     a.mov64(0, XDP_PASS)
     a.label("out").exit()
     return a.assemble()
+
+
+# ---- bpf_strncmp against a .rodata-style string ----------------------------
+_STRNCMP = 182
+
+
+def payload_prefix_drop(fd: int, prefix_len: int, payload_off: int = 42) -> bytes:
+    """Payload signature match: XDP_DROP when the `prefix_len` bytes at
+    `payload_off` (42: behind Eth + IPv4 + UDP) equal the string held in the
+    ARRAY map's value 0 -- libbpf's .rodata, named by a map-value lddw -- else
+    XDP_PASS; frames too short for the prefix pass.  bpf_strncmp(s1, s1_sz,
+    s2) compares in place, s1 aimed into the packet, and stops at a NUL the
+    two strings share.  fd: ARRAY, key 4, value >= prefix_len."""
+    a = Asm()
+    a.ldx(8, 6, 1, 0)                     # r6 = data
+    a.ldx(8, 3, 1, 8)                     # r3 = data_end
+    a.mov64(4, "r6").add64(4, payload_off + prefix_len)
+    a.mov64(0, XDP_PASS)
+    a.jmp("jgt", 4, "r3", "out")          # short frame
+    a.mov64(1, "r6").add64(1, payload_off)
+    a.mov64(2, prefix_len)
+    a.ld_map_value(3, fd, 0)
+    a.call(_STRNCMP)
+    a.mov64(1, "r0")
+    a.mov64(0, XDP_PASS)
+    a.jmp("jne", 1, 0, "out")
+    a.mov64(0, XDP_DROP)
+    a.label("out").exit()
+    return a.assemble()
