@@ -62,6 +62,11 @@ class LaunchInfo(C.Structure):
                 ("ordered", C.c_uint32)]
 
 
+class TraceLine(C.Structure):
+    """struct bpftime_amd_trace_line (include/bpftime_amd.h)"""
+    _fields_ = [("unit", C.c_uint64), ("text_off", C.c_uint32), ("text_len", C.c_uint32)]
+
+
 # (name, restype, argtypes) for every exported symbol of include/*.h
 SIGNATURES = [
     # include/ebpf-vm.h
@@ -143,6 +148,10 @@ SIGNATURES = [
     ("bpftime_object_license", C.c_char_p, [C.c_void_p]),
     ("bpftime_object_close", None, [C.c_void_p]),
     ("bpftime_amd_ringbuf_fetch", C.c_int64, [C.c_int, C.c_void_p, C.c_uint64, u64p]),
+    ("bpftime_amd_vm_set_task", C.c_int, [C.c_void_p, C.c_char_p, u64p]),
+    ("bpftime_amd_vm_get_task", C.c_int, [C.c_void_p, C.c_char_p, u64p]),
+    ("bpftime_amd_enable_trace_printk", C.c_int, [C.c_int]),
+    ("bpftime_amd_trace_read", C.c_int64, [C.POINTER(TraceLine), C.c_uint64, C.c_void_p, C.c_uint64, u64p]),
     ("bpftime_amd_syscall_attach", C.c_int, [C.c_int, C.c_int64]),
     ("bpftime_amd_syscall_detach", C.c_int, [C.c_int]),
     ("bpftime_amd_syscall_dispatch", C.c_int64, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),

@@ -404,6 +404,15 @@ struct KParams {
   uint64_t kt_stride;
   // per-lane LDS strides of the XDP ctx and the stack (lane_stride)
   uint32_t ctx_stride, stack_stride;
+  // the launching VM's task identity (bpf_get_current_uid_gid / _comm: comm
+  // NUL-terminated and zero to its end) and bpf_trace_printk's record log
+  // (trace_fmt.hpp; null: none) with its capacity in records.  Read by the
+  // scratch-stack instances only, straight from the kernel arguments
+  // (interp.hip: not copied through the SGPR barrier)
+  uint64_t task_uid_gid;
+  uint64_t task_comm[8];
+  uint8_t *trace_log;
+  uint64_t trace_cap;
 };
 
 // Where a syscall replay's fields live (include/bpftime_amd.h): record i's
@@ -434,8 +443,14 @@ struct SeqProg {
   const FInsn *fast;    // its ORDERED link (every counter add reaches memory at once)
   int64_t sys_nr;       // -1: every syscall
   uint32_t enter;       // 1 sys_enter, 0 sys_exit
-  uint32_t pad;
+  uint32_t task;        // its VM's identity: SeqParams::tasks[task]
 };
+// A VM's task identity (bpf_get_current_uid_gid / bpf_get_current_comm)
+struct SeqTask {
+  uint64_t uid_gid;
+  uint64_t comm[8];
+};
+constexpr uint32_t kSeqMaxTasks = 16;  // distinct identities among a dispatch's attached programs
 static_assert(sizeof(SeqProg) == 32, "SeqProg is read with scalar loads");
 constexpr uint32_t kSeqMaxProgs = 64;  // attached programs a thread-ordered dispatch runs (kernel arguments)
 // k_sys_seq's per-lane ctx copy: the 64-B ctx, then the record's caller
@@ -471,6 +486,9 @@ struct SeqParams {
   // private stacks, the C++ tier only
   uint32_t fast;
   SeqProg progs[kSeqMaxProgs];  // in the kernel arguments: scalar loads, no upload
+  uint8_t *trace_log;     // bpf_trace_printk's record log (trace_fmt.hpp), or null
+  uint64_t trace_cap;
+  SeqTask tasks[kSeqMaxTasks];
 };
 static_assert(sizeof(SeqParams) <= 4096, "kernel arguments");
 

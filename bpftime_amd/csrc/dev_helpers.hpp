@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include "common.hpp"
 #include "mem_guard.hpp"  // is_lds_addr, is_scratch_addr, Win, the range guard
+#include "trace_fmt.hpp"  // bpf_trace_printk: the format scanner and the log's record
 
 namespace bpftime_amd {
 
@@ -1478,11 +1479,131 @@ __device__ __noinline__ uint64_t helper_mem(uint32_t id, uint64_t a1, uint64_t a
     mem_zero(a1 + len, a2 - len);
     return 0;
   }
+  // bpf_probe_write_user(dst, src, len) (36, bpf_helper.cpp:239-299): the same
+  // copy with the length last
+  if (id == 36) {
+    const uint64_t t = a2;
+    a2 = a3;
+    a3 = t;
+  }
   // 4 / 112 / 113: one function, as in the reference
   if ((int64_t)a2 < 0) return kEfault;
   if (a2 == 0) return 0;
   if (!mem_range_ok(win, ml, a1, a2) || !mem_range_ok(win, ml, a3, a2)) return kEfault;
   mem_copy(a1, a3, a2);
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Task identity and bpf_trace_printk (15 / 16 / 6): bpf_helper.cpp:350-355,
+// :364-385, :64-76.  The identity is the launching VM's and travels in the
+// kernel arguments (KParams::task_*; per attached program in SeqParams).
+// ---------------------------------------------------------------------------
+struct TaskEnv {
+  uint64_t uid_gid;
+  uint64_t comm[8];    // NUL-terminated, zero to the end
+  uint8_t *trace_log;  // the trace log (trace_fmt.hpp), or null
+  uint64_t trace_cap;  // its records
+  uint64_t unit;       // the calling unit's global index
+};
+
+// bpf_get_current_comm(buf, size) = strncpy(buf, comm, size): comm up to and
+// with its NUL, the rest of `size` zeroed; size <= strlen(comm) copies `size`
+// bytes and adds no NUL.  The 64 bytes of `comm` are zero after the name, so
+// that is: their first min(size, 64), then zeros.  Returns 0; -EFAULT, nothing
+// written, when [buf, buf + size) is no range the guard accepts.
+__device__ __noinline__ uint64_t helper_comm(uint64_t buf, uint64_t size, const TaskEnv &te, Win win, MemLane ml) {
+  if (size == 0) return 0;
+  if (!mem_range_ok(win, ml, buf, size)) return kEfault;
+  const uint64_t lim = size < 64 ? size : 64;
+#pragma unroll
+  for (uint32_t j = 0; j < 8; j++) {
+    uint64_t w = te.comm[j];
+    for (uint32_t b = 0; b < 8 && 8 * j + b < lim; b++, w >>= 8) mem_st8(buf + 8 * j + b, (uint8_t)w);
+  }
+  if (size > 64) mem_zero(buf + 64, size - 64);
+  return 0;
+}
+
+// bpf_trace_printk(fmt, fmt_size, a3, a4, a5): one record in the trace log,
+// formatted by the host when it reads the log (bpftime_amd_trace_read).
+// Returns 0 whether the record was stored or the log was full, as the
+// reference always does; -EINVAL / -EFAULT (trace_fmt.hpp) log
+// nothing.  Every byte read -- the format, a %s argument's string -- lies in a
+// range mem_room gave; every loop is per lane and bounded by a cap.
+// Reservation: the calling lanes of the wave are ranked by lane id, one lane
+// adds the group's size to `tail` with one relaxed agent-scope fetch-and-add,
+// lane of rank r takes ticket base + r; a ticket at or past the capacity
+// counts into `lost` (one add per wave).  No lane waits on another.
+__device__ __noinline__ uint64_t helper_trace(uint64_t fmt, uint64_t fmt_size, uint64_t a3, uint64_t a4, uint64_t a5,
+                                              const TaskEnv &te, Win win, MemLane ml) {
+  constexpr uint64_t kEinval = (uint64_t)(int64_t)kTraceEinval;
+  const int fl = trace_fmt_len([&](uint32_t i) { return mem_ld8(fmt + i); }, fmt_size, mem_room(win, ml, fmt));
+  if (fl < 0) return (uint64_t)(int64_t)fl;
+  const uint32_t flen = (uint32_t)fl;
+  TraceConv cv[kTraceMaxArgs];
+  const int n = trace_scan([&](uint32_t i) { return mem_ld8(fmt + i); }, flen, cv);
+  if (n < 0) return kEinval;
+  if (!te.trace_log) return 0;
+  // the %s arguments: state and length, bounded by the room of the region
+  // the string starts in, the per-string cap and the precision
+  const uint64_t args[3] = {a3, a4, a5};
+  uint8_t kind[3] = {TK_NONE, TK_NONE, TK_NONE}, state[3] = {0, 0, 0}, slen[3] = {0, 0, 0};
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    if (a >= n) continue;
+    kind[a] = cv[a].conv == 's' ? TK_STR : TK_INT;
+    if (kind[a] != TK_STR) continue;
+    const uint64_t s = args[a];
+    if (s == 0) {
+      state[a] = TS_NULL;
+      continue;
+    }
+    const uint64_t sroom = mem_room(win, ml, s);
+    if (sroom == 0) {
+      state[a] = TS_EFAULT;
+      continue;
+    }
+    const uint64_t lim = trace_str_lim(sroom, cv[a].prec);
+    uint32_t l = 0;
+    while (l < lim && mem_ld8(s + l) != 0) l++;
+    slen[a] = (uint8_t)l;
+  }
+  // the wave's calling lanes, ranked by lane id
+  const uint64_t active = __ballot(1);
+  const uint32_t me = __lane_id();
+  const uint32_t leader = (uint32_t)__builtin_ctzll(active);
+  const uint32_t cnt = (uint32_t)__builtin_popcountll(active);
+  const uint32_t rank = (uint32_t)__builtin_popcountll(active & ((1ull << me) - 1));
+  uint64_t base = 0;
+  if (me == leader) {
+    base = __hip_atomic_fetch_add((uint64_t *)te.trace_log, (uint64_t)cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint64_t fit = base < te.trace_cap ? te.trace_cap - base : 0;
+    if (fit < cnt)
+      __hip_atomic_fetch_add((uint64_t *)(te.trace_log + 8), (uint64_t)cnt - fit, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+  }
+  base = __shfl(base, leader);
+  const uint64_t ticket = base + rank;
+  if (ticket >= te.trace_cap) return 0;
+  const uint64_t rec = (uint64_t)(uintptr_t)te.trace_log + kTraceHdrBytes + ticket * kTraceRecBytes;
+  *(volatile uint64_t *)(rec + 0) = te.unit;
+  *(volatile uint64_t *)(rec + 8) = a3;
+  *(volatile uint64_t *)(rec + 16) = a4;
+  *(volatile uint64_t *)(rec + 24) = a5;
+  *(volatile uint64_t *)(rec + 32) = (uint64_t)flen | ((uint64_t)n << 8) | ((uint64_t)kind[0] << 16) |
+                                     ((uint64_t)kind[1] << 24) | ((uint64_t)kind[2] << 32) |
+                                     ((uint64_t)state[0] << 40) | ((uint64_t)state[1] << 48) |
+                                     ((uint64_t)state[2] << 56);
+  *(volatile uint64_t *)(rec + 40) = (uint64_t)slen[0] | ((uint64_t)slen[1] << 8) | ((uint64_t)slen[2] << 16);
+  mem_copy(rec + 48, fmt, flen);
+  mem_st8(rec + 48 + flen, 0);
+#pragma unroll
+  for (int a = 0; a < 3; a++)
+    if (kind[a] == TK_STR && state[a] == TS_OK) {
+      mem_copy(rec + 144 + 48 * a, args[a], slen[a]);
+      mem_st8(rec + 144 + 48 * a + slen[a], 0);
+    }
   return 0;
 }
 

@@ -46,12 +46,18 @@ namespace bpftime_amd {
 template <bool BLOOM>
 __device__ __forceinline__ uint64_t call_helper(uint32_t id, uint64_t a1, uint64_t a2, uint64_t a3, uint64_t a4,
                                                 uint64_t a5, const DMap *maps, uint32_t ncpu, uint64_t seed,
-                                                LaneEnv &env, uint32_t *err, const Win &win, const MemLane &ml) {
+                                                LaneEnv &env, uint32_t *err, const Win &win, const MemLane &ml,
+                                                const TaskEnv &te) {
   if constexpr (BLOOM) {
+    // the launching VM's identity and bpf_trace_printk's record log --
+    // dev_helpers.hpp helper_comm / helper_trace
+    if (id == 15) return te.uid_gid;
+    if (id == 16) return helper_comm(a1, a2, te, win, ml);
+    if (id == 6) return helper_trace(a1, a2, a3, a4, a5, te, win, ml);
     // bpf_probe_read* / bpf_probe_read_*_str / bpf_strncmp: byte ranges of
     // run-time length, checked against the windows and the lane's own stack
     // and ctx extents -- dev_helpers.hpp helper_mem
-    if (id == 4 || id == 112 || id == 113 || id == 45 || id == 114 || id == 115 || id == 182)
+    if (id == 4 || id == 112 || id == 113 || id == 45 || id == 114 || id == 115 || id == 182 || id == 36)
       return helper_mem(id, a1, a2, a3, win, ml);
     // a QUEUE / STACK map: push / pop / peek, and lookup (a peek that returns
     // the slot), update (a push, the key ignored) and delete (a pop that
@@ -70,6 +76,7 @@ __device__ __forceinline__ uint64_t call_helper(uint32_t id, uint64_t a1, uint64
     case 1: return helper_lookup(maps, a1, a2, env);
     case 2: return helper_update(maps, a1, a2, a3, a4, env);
     case 3: return helper_delete(maps, a1, a2, env);
+    // (bpf_ktime_get_boot_ns / _coarse_ns arrive as 5 too: loader.cpp load_program)
     case 5: return env.kt_on ? env.ktime : (uint64_t)__builtin_amdgcn_s_memrealtime() * 10ull;
     case 7: {
       uint64_t x = seed * 0x9E3779B97F4A7C15ull;
@@ -1154,9 +1161,19 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(4))) void k_
         // its stack, and the XDP ctx copy -- other kinds' ctx is the unit)
         const MemLane ml{stack_top - kStackSize, KIND == CTX_XDP ? (uint64_t)(uintptr_t)my_ctx : 0, kStackSize,
                          KIND == CTX_XDP ? kXdpCtxBytes : 0u};
+        // the VM's identity and the trace log: kernel arguments only the
+        // scratch-stack instances read
+        TaskEnv te{};
+        if constexpr (BIGSTACK) {
+          te.uid_gid = pin.task_uid_gid;
+          for (int j = 0; j < 8; j++) te.comm[j] = pin.task_comm[j];
+          te.trace_log = pin.trace_log;
+          te.trace_cap = pin.trace_cap;
+          te.unit = p.first_unit + unit;
+        }
         const uint64_t rv = call_helper<BIGSTACK>(c.call_id, R[1 * kBlock], R[2 * kBlock], R[3 * kBlock], R[4 * kBlock],
                                         R[5 * kBlock], p.maps, p.ncpu,
-                                        (p.first_unit + unit) ^ ((uint64_t)c.steps << 40), env, &cerr, c.win, ml);
+                                        (p.first_unit + unit) ^ ((uint64_t)c.steps << 40), env, &cerr, c.win, ml, te);
         R[0] = rv;
         miss_fd = env.miss_fd;
         miss_hash = env.miss_hash;
@@ -1640,10 +1657,20 @@ __global__ __launch_bounds__(kBlock) void k_sys_seq(SeqParams p) {
           // and the callback's ctx copy, {id, args} or {id, ret}
           const uint32_t sbytes = fast ? kLdsStackMax : kStackSize;
           const MemLane ml{stack_top - sbytes, (uint64_t)(uintptr_t)ctx, sbytes, enter ? 64u : 24u};
+          // the attached program's VM's identity (SeqParams::tasks), the trace log
+          TaskEnv te{};
+          if (cid == 6 || cid == 15 || cid == 16) {
+            const SeqTask *tk = &p.tasks[__builtin_amdgcn_readfirstlane(sp->task) % kSeqMaxTasks];
+            te.uid_gid = tk->uid_gid;
+            for (int j = 0; j < 8; j++) te.comm[j] = tk->comm[j];
+            te.trace_log = p.trace_log;
+            te.trace_cap = p.trace_cap;
+            te.unit = idx;
+          }
           const uint64_t rv = cid == kTailHelper ? 0
                               : call_helper<true>(cid, R[1 * kBlock], R[2 * kBlock], R[3 * kBlock], R[4 * kBlock],
                                             R[5 * kBlock], p.maps, p.ncpu, idx ^ ((uint64_t)c.steps << 40), env,
-                                            &cerr, c.win, ml);
+                                            &cerr, c.win, ml, te);
           if (cid == kTailHelper) cerr = E_BADOP;  // (the host refuses such programs)
           R[0] = rv;
           miss_fd = env.miss_fd;

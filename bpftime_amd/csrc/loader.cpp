@@ -30,6 +30,10 @@ bool device_helper_supported(uint32_t id) {
     case 4: case 112: case 113:   // bpf_probe_read / _user / _kernel
     case 45: case 114: case 115:  // bpf_probe_read_str / _user_str / _kernel_str
     case 182:                     // bpf_strncmp
+    case 6:                       // bpf_trace_printk (a record in the trace log)
+    case 15: case 16:             // bpf_get_current_uid_gid / _comm (the launching VM's identity)
+    case 36:                      // bpf_probe_write_user
+    case 125: case 160:           // bpf_ktime_get_boot_ns / _coarse_ns (helper 5's clock)
     case kTailHelper:
       return true;
   }
@@ -44,6 +48,14 @@ static bool mem_copy_helper(int64_t id) {
   return id == 4 || id == 112 || id == 113 || id == 45 || id == 114 || id == 115;
 }
 static bool mem_helper(int64_t id) { return mem_copy_helper(id) || id == 182; }
+// ... and the rest of the out-of-line family (helper_mem / helper_comm /
+// helper_trace): probe_write_user(dst, src, len) writes r1's range and reads
+// r2's; get_current_comm(buf, size) writes r1's; trace_printk(fmt, fmt_size,
+// a3, a4, a5) reads r1's and, for a %s, what r3..r5 point to;
+// get_current_uid_gid takes nothing
+static bool task_trace_helper(int64_t id) { return id == 6 || id == 15 || id == 16 || id == 36; }
+// the helpers that write a range of run-time length through r1
+static bool writes_r1_helper(int64_t id) { return mem_copy_helper(id) || id == 16 || id == 36; }
 
 static std::string fmt(const char *f, ...) __attribute__((format(printf, 1, 2)));
 static std::string fmt(const char *f, ...) {
@@ -244,6 +256,9 @@ static DInsn decode_one(const std::vector<RawInsn> &in, uint32_t i) {
 static int helper_arity(uint32_t id) {
   switch (id) {
     case 5: case 7: case 8: return 0;          // ktime_get_ns, get_prandom_u32, get_smp_processor_id
+    case 15: case 125: case 160: return 0;     // get_current_uid_gid, ktime_get_boot_ns / _coarse_ns
+    case 16: return 2;                         // get_current_comm(buf, size)
+    case 36: return 3;                         // probe_write_user(dst, src, len)
     case 1: case 3: case 44: case 65: return 2;  // map_lookup/delete_elem, xdp_adjust_head/tail
     case 88: case 89: return 2;                // map_pop/peek_elem(map, value)
     case 87: return 3;                         // map_push_elem(map, value, flags)
@@ -491,7 +506,8 @@ int load_program(const RawInsn *code, size_t n, const std::map<size_t, size_t> &
         }
         return -EINVAL;
       }
-      if (!device_helper_supported((uint32_t)cur.imm)) {
+      // (bpf_trace_printk: only once the host enabled it, runtime.hpp trace_printk_on)
+      if (!device_helper_supported((uint32_t)cur.imm) || (cur.imm == 6 && !rt().trace_printk_on.load())) {
         auto it = helper_names.find((size_t)cur.imm);
         err = "helper " + std::to_string(cur.imm) + " (" + (it != helper_names.end() ? it->second : "?") +
               ") has no device implementation at PC " + std::to_string(i);
@@ -500,7 +516,17 @@ int load_program(const RawInsn *code, size_t n, const std::map<size_t, size_t> &
       if (cur.imm == 3) out.may_delete = true;
       if (cur.imm == 87 || cur.imm == 88 || cur.imm == 89) out.bloom = true;
       if (mem_helper(cur.imm)) out.bloom = true;  // (helper_mem: the scratch-stack kernels' too)
+      if (task_trace_helper(cur.imm)) out.bloom = true;  // (helper_comm / helper_trace: beside helper_mem)
+      if (cur.imm == 6) out.trace_printk = true;
       if (cur.imm == 58 || cur.imm == 187) out.sets_retval = true;
+      // bpf_ktime_get_boot_ns / bpf_ktime_get_coarse_ns: a batch has one
+      // clock source, so both are helper 5 from here on -- in the analyses,
+      // in both tiers (the asm tier's CALL_REC included) and in the kernels,
+      // whose helper switch stays as it is (two more case labels in it
+      // changed the spill counts of every LDS-stack instance of k_interp).
+      // (An unwind index naming 125 / 160 therefore never fires: a clock
+      // does not return 0.)
+      if (cur.imm == 125 || cur.imm == 160) cur.imm = 5;
     } else if (cur.code == 0x18) {
       if (i + 1 == n) {
         err = "Unable to patch lddw instructions at " + std::to_string(i) + ", it's the last instruction";
@@ -905,7 +931,7 @@ static bool pointer_kinds(const std::vector<DInsn> &p, const std::vector<uint8_t
         const PVal m = st[1];
         // (a copy helper's destination of run-time length inside the ctx may
         // reach its packet pointers)
-        if (mem_copy_helper(d.hi) && st[1].kind == P_CTX) ctx_written = true;
+        if (writes_r1_helper(d.hi) && st[1].kind == P_CTX) ctx_written = true;
         // (not of a QUEUE / STACK: the slot a peek returns is no element of a keyed value array)
         st[0] = (d.hi == 1 && m.kind == P_MAPFD && map_rec(m.id) && !qs_type(map_rec(m.id)->type))
                     ? PVal{P_MVNULL, 0, m.id}
@@ -1035,6 +1061,13 @@ static void accesses(const std::vector<DInsn> &p, uint32_t i, const std::vector<
   };
   switch (id) {
     case 5: case 7: case 8: case 131: case 44: case 65: return;  // no memory (ctx helpers: unit-local)
+    case 15: case 125: case 160: return;  // the VM's identity, the clock: no memory
+    case 16: arg(1); return;              // get_current_comm writes r1's range
+    case 36: arg(1); arg(2); return;      // probe_write_user(dst, src, len)
+    // trace_printk reads the format and what a %s argument points to: r3..r5
+    // of a pointer kind (an argument the kinds cannot place may be a pointer
+    // into any map: the lattice has no scalar kind)
+    case 6: arg(1); arg(3); arg(4); arg(5); return;
     case 1: arg(2); return;
     case 2: arg(2); arg(3); map_values(); return;
     case 3: arg(2); map_values(); return;
@@ -1136,6 +1169,7 @@ static void const_loads(const std::vector<DInsn> &p, const std::vector<uint8_t> 
         switch (d.hi) {
           case 1: case 5: case 7: case 8: case 14: case 28: case 58: case 187: case 130:
           case 131: case 132: case 133: case 44: case 65:
+          case 6: case 15: case 125: case 160:  // (trace_printk reads only, into the log)
             break;  // no array-map writes (ring memory, the unit's ctx, dispatch state)
           case 88: case 89:  // pop / peek of a QUEUE / STACK write *value
             writes.push_back(loc_of(p, st[2], 0, kUnknownLen));
@@ -1148,6 +1182,7 @@ static void const_loads(const std::vector<DInsn> &p, const std::vector<uint8_t> 
             writes.push_back(loc_of(p, st[3], 0, kUnknownLen));
             break;
           case 4: case 112: case 113: case 45: case 114: case 115:  // probe_read*(dst, ...) write *dst
+          case 16: case 36:  // get_current_comm(buf, ...), probe_write_user(dst, ...)
             writes.push_back(loc_of(p, st[1], 0, kUnknownLen));
             break;
           case 182:  // strncmp: reads only
@@ -1396,9 +1431,11 @@ static void tail_save_masks(const std::vector<DInsn> &p, const std::vector<std::
       case 44: case 65: ctx_bytes(0, 16); break;  // adjust_head / adjust_tail: data, data_end
       case 189: write(st[3], 0, 1 << 16); break;  // xdp_load_bytes(ctx, off, to, len)
       case 4: case 112: case 113: case 45: case 114: case 115:
-        write(st[1], 0, 1 << 16);  // probe_read*(dst, size, src) write *dst
+      case 16: case 36:
+        write(st[1], 0, 1 << 16);  // probe_read*(dst, size, src), get_current_comm, probe_write_user write *dst
         break;
       case 182: break;  // strncmp: reads only
+      case 6: case 15: case 125: case 160: break;  // trace_printk reads only; no arguments
       default:
         if (d.hi != kRetHelper) {
           cm = 0x3f;
@@ -1495,7 +1532,26 @@ static void map_effects(const std::vector<DInsn> &prog, const std::vector<std::v
           case 1: case 89: mark(fd, FX_READ); break;                    // map_lookup_elem, map_peek_elem
           case 2: case 3: case 130: case 131: case 87: case 88: mark(fd, FX_WRITE); break;  // update, delete, ringbuf output / reserve, push, pop
           case 5: case 7: case 8: case 14: case 28: case 44: case 58: case 65: case 132: case 133: case 187: case 189:
+          case 15: case 125: case 160:
             break;  // no map effects (132 / 133 finish a reservation 131 marked)
+          case 16: {  // get_current_comm writes through r1
+            const int32_t t1 = target(i, st[1], 0, 1);
+            if (t1 != -2) mark(t1, FX_WRITE);
+            break;
+          }
+          case 36: {  // probe_write_user(dst, src, len): writes through r1, reads through r2
+            const int32_t t1 = target(i, st[1], 0, 1), t2 = target(i, st[2], 0, 1);
+            if (t1 != -2) mark(t1, FX_WRITE);
+            if (t2 != -2) mark(t2, FX_READ);
+            break;
+          }
+          case 6: {  // trace_printk reads the format and what its %s arguments point to
+            for (int r : {1, 3, 4, 5}) {
+              const int32_t t = target(i, st[r], 0, 1);
+              if (t != -2) mark(t, FX_READ);
+            }
+            break;
+          }
           case 4: case 112: case 113: case 45: case 114: case 115: case 182: {
             // probe_read* / probe_read*_str write through r1 and read through
             // r3, strncmp reads through both: map effects when the pointer
@@ -1580,7 +1636,7 @@ void build_fast(const LoadOut &lo, bool xdp, FastForm &out) {
   if (kinds_ok) map_effects(prog, in, out);  // (else any_fx stays: every map, read and written)
   for (size_t i = 0; kinds_ok && i < prog.size(); i++) {
     const DInsn &d = prog[i];
-    const bool copies = d.op == X_CALL && mem_copy_helper(d.hi);  // (writes through r1)
+    const bool copies = d.op == X_CALL && writes_r1_helper(d.hi);  // (writes through r1)
     if (d.op != X_ST && d.op != X_STX && d.op != X_RMW_ADD && d.op != X_ATOMIC && !copies) continue;
     const uint8_t k = in[i][copies ? 1 : d.dst].kind;
     if (k != P_UNDEF && k != P_STK && k != P_MAPVAL && k != P_CONST) out.stores_unit = true;

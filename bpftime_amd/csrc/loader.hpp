@@ -96,6 +96,7 @@ struct LoadOut {
   uint32_t fused_rmw = 0;
   uint32_t comb_entries = 0;  // per-block LDS combining entries (0 = none needed)
   bool bloom = false;         // calls bpf_map_push / pop / peek_elem or names a BLOOM_FILTER / QUEUE / STACK: scratch-stack kernels only
+  bool trace_printk = false;  // calls bpf_trace_printk: the runtime's trace log must exist before a launch
   bool may_delete = false;    // calls map_delete_elem: hash lookup indexes stop being valid
   bool tail_call = false;     // calls bpf_tail_call: linked with the prog arrays' targets at launch
   bool sets_retval = false;   // calls bpf_override_return (58) / bpf_set_retval (187)

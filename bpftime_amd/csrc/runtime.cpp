@@ -135,6 +135,7 @@ void bpftime_amd_reset(void) {
   syscall_detach_all();  // the link-made attachments and the direct ones
   if (r.d_maptab) hipMemset(r.d_maptab, 0, sizeof(DMap) * kMaxFds);
   r.arena_used = 0;
+  r.trace_printk_on = false;
   r.prog_gen++;  // tail-call images linked before the reset relink
 }
 

@@ -99,6 +99,11 @@ struct Runtime {
   uint32_t ncpu = 64;
   std::string last_error;
   uint64_t prog_gen = 1;        // bumped when a prog, a prog array or its contents change
+  // bpf_trace_printk (6) on the device: off until bpftime_amd_enable_trace_printk(1)
+  // (and again after bpftime_amd_reset).  While off the helper is no default
+  // helper and a program that calls it is refused at load as before: a host
+  // that never asked for the record log does not get one.
+  std::atomic<bool> trace_printk_on{false};
 
   int ensure_device();          // lazily picks the current device, allocates arena + table
   uint64_t arena_alloc(uint64_t bytes);

@@ -25,8 +25,42 @@
 #include "../../include/bpftime_amd.h"
 #include "loader.hpp"
 #include "runtime.hpp"
+#include "trace_fmt.hpp"
 
 namespace bpftime_amd {
+// bpf_trace_printk's record log (trace_fmt.hpp): one per process, device
+// memory of the runtime's own, made when the first program that calls helper
+// 6 is loaded.  BPFTIME_AMD_TRACE_RECORDS (read once, here) sets its records.
+struct TraceLog {
+  std::mutex mu;
+  uint8_t *d = nullptr;
+  uint64_t cap = 0;
+  uint64_t consumed = 0;  // records the host has delivered since the log was last empty
+};
+static TraceLog &trace_log() {
+  static TraceLog t;
+  return t;
+}
+static int trace_log_ensure() {
+  TraceLog &t = trace_log();
+  std::lock_guard<std::mutex> g(t.mu);
+  if (t.d) return 0;
+  uint64_t cap = kTraceDefaultRecords;
+  if (const char *e = getenv("BPFTIME_AMD_TRACE_RECORDS")) {
+    const uint64_t v = strtoull(e, nullptr, 0);
+    if (v >= 1 && v <= (1ull << 26)) cap = v;
+  }
+  uint8_t *d = nullptr;
+  if (hipMalloc((void **)&d, kTraceHdrBytes + cap * kTraceRecBytes) != hipSuccess) return -1;
+  if (hipMemset(d, 0, kTraceHdrBytes) != hipSuccess) {
+    hipFree(d);
+    return -1;
+  }
+  t.d = d;
+  t.cap = cap;
+  t.consumed = 0;
+  return 0;
+}
 extern "C" hipError_t bpftime_amd_launch_interp(const KParams *p, uint32_t kind, bool big_stack, uint32_t grid,
                                                 uint32_t ordered, uint32_t block, hipStream_t stream);
 
@@ -275,6 +309,10 @@ struct Image {
   }
   // device copy of the decoded program + both threaded forms
   int upload(LoadOut &&out, std::string &err) {
+    if (out.trace_printk && trace_log_ensure() < 0) {
+      err = "trace log: device alloc failed";
+      return -1;
+    }
     build_fast(out, true, fx);
     build_fast(out, false, fr);
     out.comb_entries = (fx.needs_comb || fr.needs_comb) ? kComb : 0;
@@ -330,6 +368,12 @@ class Mi355xVm {
   int unwind_idx = -1;
   uint32_t ctx_kind = CTX_RAW;
   uint64_t step_limit = 1ull << 22;
+  // task identity (bpf_get_current_uid_gid / bpf_get_current_comm): the
+  // reference's answers for the launching process until
+  // bpftime_amd_vm_set_task; comm is zero from its NUL to the end
+  uint64_t task_uid_gid = 0;
+  char task_comm[64] = {};
+  std::mutex task_mu;
 
   bool loaded = false;
   std::mutex img_mu;                 // guards img (replaced by tail-call relinks)
@@ -367,6 +411,21 @@ class Mi355xVm {
     lddw.map_val = bpftime_amd_map_val;
     const char *sl = getenv("BPFTIME_AMD_STEP_LIMIT");
     if (sl) step_limit = strtoull(sl, nullptr, 0);
+    // bpf_helper.cpp:350-355: the gid in both halves; :364-385: the basename
+    // of /proc/self/exe
+    task_uid_gid = ((uint64_t)getgid() << 32) | (uint64_t)getgid();
+    char exe[4096];
+    const ssize_t k = readlink("/proc/self/exe", exe, sizeof(exe) - 1);
+    if (k > 0) {
+      exe[k] = 0;
+      const char *base = strrchr(exe, '/');
+      strncpy(task_comm, base ? base + 1 : exe, sizeof(task_comm) - 1);
+    }
+  }
+  void task_into(uint64_t &uid_gid, uint64_t comm[8]) {
+    std::lock_guard<std::mutex> g(task_mu);
+    uid_gid = task_uid_gid;
+    memcpy(comm, task_comm, 64);
   }
   ~Mi355xVm() {
     if (ev_t0) hipEventDestroy(ev_t0);
@@ -743,6 +802,9 @@ int Mi355xVm::exec_batch(const ebpf_batch *b) {
     p.kt_stride = b->ktime_stride;
   }
   p.pid_tgid = ((uint64_t)(uint32_t)getpid() << 32) | (uint32_t)syscall(SYS_gettid);
+  task_into(p.task_uid_gid, p.task_comm);
+  p.trace_log = trace_log().d;  // (made at load when the program calls helper 6)
+  p.trace_cap = trace_log().cap;
   p.arena_lo = (uint64_t)(uintptr_t)r.arena;
   p.arena_hi = p.arena_lo + r.arena_size;
   p.step_limit = step_limit;
@@ -1349,6 +1411,7 @@ int64_t seq_dispatch(const std::vector<SeqAttach> &progs, const SysLayout &lay, 
   std::vector<int> lpm_w;
   uint32_t lpm_updates = 0;
   uint64_t steps = 0;
+  uint32_t ntasks = 0;
   // the asm tier runs the callbacks when every stack fits the LDS stacks and
   // the threads are at most kSeqAsmThreads: measured (profiles/
   // r06_seq_xover.txt, syscount's pair) 2-3.7x the C++ tier up to 8192
@@ -1384,6 +1447,19 @@ int64_t seq_dispatch(const std::vector<SeqAttach> &progs, const SysLayout &lay, 
     q.fast = f;
     q.sys_nr = a.sys_nr;
     q.enter = a.enter ? 1 : 0;
+    {  // its VM's identity: one table entry per distinct identity
+      SeqTask tk{};
+      vm->task_into(tk.uid_gid, tk.comm);
+      uint32_t ti = 0;
+      while (ti < ntasks && memcmp(&p.tasks[ti], &tk, sizeof(tk)) != 0) ti++;
+      if (ti == ntasks) {
+        if (ntasks == kSeqMaxTasks)
+          return fail("the attached programs' VMs have more than " + std::to_string(kSeqMaxTasks) +
+                      " distinct task identities");
+        p.tasks[ntasks++] = tk;
+      }
+      q.task = ti;
+    }
     may_delete |= im->prog.may_delete;
     names_lpm |= im->fr.names_lpm;
     {  // QUEUE / STACK maps: lanes in thread order are not record order across threads
@@ -1421,6 +1497,8 @@ int64_t seq_dispatch(const std::vector<SeqAttach> &progs, const SysLayout &lay, 
   p.step_limit = steps;
   p.pid_tgid = ((uint64_t)(uint32_t)getpid() << 32) | (uint32_t)syscall(SYS_gettid);
   p.err_count = err;
+  p.trace_log = trace_log().d;
+  p.trace_cap = trace_log().cap;
   p.exact = ordered ? 1 : 0;
   p.fast = fast ? 1 : 0;
   // the map upkeep exec_batch does before a launch, for the union of the
@@ -1587,9 +1665,14 @@ int bpftime_amd_register_default_helpers(struct ebpf_vm *vm) {
            {87, "bpf_map_push_elem"},        {88, "bpf_map_pop_elem"},   {89, "bpf_map_peek_elem"},
            {4, "bpf_probe_read"},            {112, "bpf_probe_read_user"}, {113, "bpf_probe_read_kernel"},
            {45, "bpf_probe_read_str"},       {114, "bpf_probe_read_user_str"},
-           {115, "bpf_probe_read_kernel_str"}, {182, "bpf_strncmp"}};
+           {115, "bpf_probe_read_kernel_str"}, {182, "bpf_strncmp"},
+           {15, "bpf_get_current_uid_gid"},  {16, "bpf_get_current_comm"},
+           {36, "bpf_probe_write_user"},     {125, "bpf_ktime_get_boot_ns"},
+           {160, "bpf_ktime_get_coarse_ns"}};
   int err = 0;
   for (auto &e : h) err |= ebpf_register(vm, e.id, e.name, nullptr);
+  // ... and bpf_trace_printk once the host enabled it (bpftime_amd_enable_trace_printk)
+  if (rt().trace_printk_on.load()) err |= ebpf_register(vm, 6, "bpf_trace_printk", nullptr);
   return err ? -1 : 0;
 }
 
@@ -1659,6 +1742,79 @@ int bpftime_amd_vm_last_launch(const struct ebpf_vm *vm, struct bpftime_amd_laun
 }
 
 void bpftime_amd_set_step_limit(struct ebpf_vm *vm, uint64_t limit) { vm->impl->step_limit = limit; }
+
+int bpftime_amd_vm_set_task(struct ebpf_vm *vm, const char *comm, const uint64_t *uid_gid) {
+  if (!vm) return -1;
+  if (comm && strnlen(comm, 64) > 63) return -1;  // (the VM unchanged)
+  std::lock_guard<std::mutex> g(vm->impl->task_mu);
+  if (comm) {
+    memset(vm->impl->task_comm, 0, sizeof(vm->impl->task_comm));
+    strncpy(vm->impl->task_comm, comm, 63);
+  }
+  if (uid_gid) vm->impl->task_uid_gid = *uid_gid;
+  return 0;
+}
+
+int bpftime_amd_vm_get_task(const struct ebpf_vm *vm, char *comm, uint64_t *uid_gid) {
+  if (!vm) return -1;
+  std::lock_guard<std::mutex> g(vm->impl->task_mu);
+  if (comm) memcpy(comm, vm->impl->task_comm, 64);
+  if (uid_gid) *uid_gid = vm->impl->task_uid_gid;
+  return 0;
+}
+
+int bpftime_amd_enable_trace_printk(int on) {
+  const bool was = rt().trace_printk_on.exchange(on != 0);
+  return was ? 1 : 0;
+}
+
+int64_t bpftime_amd_trace_read(struct bpftime_amd_trace_line *lines, uint64_t max_lines, char *text,
+                               uint64_t text_cap, uint64_t *lost) {
+  TraceLog &t = trace_log();
+  std::lock_guard<std::mutex> g(t.mu);
+  if (!t.d) return -1;
+  if (hipDeviceSynchronize() != hipSuccess) return -1;  // the batches still writing records first
+  uint64_t hdr[2] = {0, 0};
+  if (hipMemcpy(hdr, t.d, sizeof(hdr), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  const uint64_t stored = hdr[0] < t.cap ? hdr[0] : t.cap;
+  if (lost) *lost += hdr[1];
+  if (hdr[1] && hipMemset(t.d + 8, 0, 8) != hipSuccess) return -1;
+  uint64_t want = stored > t.consumed ? stored - t.consumed : 0;
+  if (!lines || !text) max_lines = 0;
+  if (want > max_lines) want = max_lines;
+  int64_t delivered = 0;
+  uint64_t used = 0;
+  std::vector<TraceRec> recs;
+  const uint64_t kChunk = 4096;
+  bool full = false;
+  for (uint64_t at = 0; at < want && !full; at += kChunk) {
+    const uint64_t k = std::min(kChunk, want - at);
+    recs.resize(k);
+    if (hipMemcpy(recs.data(), t.d + kTraceHdrBytes + (t.consumed + at) * kTraceRecBytes, k * kTraceRecBytes,
+                  hipMemcpyDeviceToHost) != hipSuccess)
+      return -1;
+    for (uint64_t j = 0; j < k; j++) {
+      char line[1024];
+      const int len = trace_format(recs[j], line, sizeof(line));
+      if (len < 0 || used + (uint64_t)len + 1 > text_cap) {  // only lines that fit whole
+        full = true;
+        break;
+      }
+      memcpy(text + used, line, (size_t)len + 1);
+      lines[delivered].unit = recs[j].unit;
+      lines[delivered].text_off = (uint32_t)used;
+      lines[delivered].text_len = (uint32_t)len;
+      used += (uint64_t)len + 1;
+      delivered++;
+    }
+  }
+  t.consumed += (uint64_t)delivered;
+  if (t.consumed >= stored) {  // fully consumed: the tickets start over
+    if (hipMemset(t.d, 0, 8) != hipSuccess) return -1;
+    t.consumed = 0;
+  }
+  return delivered;
+}
 
 float bpftime_amd_last_batch_ms(struct ebpf_vm *vm) {
   Mi355xVm *v = vm ? vm->impl : nullptr;

@@ -80,6 +80,11 @@ BPF_FUNC_probe_read_kernel = 113
 BPF_FUNC_probe_read_user_str = 114
 BPF_FUNC_probe_read_kernel_str = 115
 BPF_FUNC_strncmp = 182
+BPF_FUNC_get_current_uid_gid = 15
+BPF_FUNC_get_current_comm = 16
+BPF_FUNC_probe_write_user = 36
+BPF_FUNC_ktime_get_boot_ns = 125
+BPF_FUNC_ktime_get_coarse_ns = 160
 
 # map types (linux/bpf.h)
 BPF_MAP_TYPE_HASH = 1

@@ -828,3 +828,38 @@ def payload_prefix_drop(fd: int, prefix_len: int, payload_off: int = 42) -> byte
     a.mov64(0, XDP_DROP)
     a.label("out").exit()
     return a.assemble()
+
+
+# ---- a sys_enter tracer: filter on comm, print, count per uid ---------------
+_TRACE_PRINTK, _GET_CURRENT_UID_GID, _GET_CURRENT_COMM = 6, 15, 16
+
+
+def sys_enter_tracer(comm_fd: int, counts_fd: int) -> bytes:
+    """A syscall-tracepoint program in the style of execsnoop / syscount: it
+    reads the task's comm (bpf_get_current_comm, 16 bytes, the last forced to
+    NUL as TASK_COMM_LEN does), returns unless its first 15 bytes equal the
+    filter held in the ARRAY map's value 0 (.rodata, a map-value lddw;
+    bpf_strncmp), prints "<pid> <comm>" with bpf_trace_printk and adds 1 to
+    the caller's uid in a HASH map (u32 -> u64, created on first use).
+    Loads once the host enabled the helper (vm.enable_trace_printk).
+    comm_fd: ARRAY, key 4, value >= 16.  counts_fd: HASH, key 4, value 8."""
+    a = Asm()
+    a.mov64(1, "r10").add64(1, -16).mov64(2, 16).call(_GET_CURRENT_COMM)
+    a.st(1, 10, -1, 0)
+    a.mov64(1, "r10").add64(1, -16).mov64(2, 15).ld_map_value(3, comm_fd, 0).call(_STRNCMP)
+    a.jmp("jne", 0, 0, "out")
+    a.call(BPF_FUNC_get_current_pid_tgid).mov64(6, "r0").alu64("rsh", 6, 32)
+    a.lddw(2, int.from_bytes(b"%d %s\n\0\0", "little")).stx(8, 10, -24, "r2")
+    a.mov64(1, "r10").add64(1, -24).mov64(2, 7).mov64(3, "r6").mov64(4, "r10").add64(4, -16)
+    a.call(_TRACE_PRINTK)
+    a.call(_GET_CURRENT_UID_GID).stx(4, 10, -28, "r0")
+    a.ld_map_fd(1, counts_fd).mov64(2, "r10").add64(2, -28).call(1)
+    a.jmp("jne", 0, 0, "add")
+    a.st(8, 10, -40, 0)
+    a.ld_map_fd(1, counts_fd).mov64(2, "r10").add64(2, -28).mov64(3, "r10").add64(3, -40).mov64(4, 1)  # BPF_NOEXIST
+    a.call(2)
+    a.ld_map_fd(1, counts_fd).mov64(2, "r10").add64(2, -28).call(1)
+    a.jmp("jeq", 0, 0, "out")
+    a.label("add").mov64(2, 1).atomic(8, ATOMIC_ADD, 0, 0, "r2")
+    a.label("out").mov64(0, 0).exit()
+    return a.assemble()

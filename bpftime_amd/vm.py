@@ -14,7 +14,7 @@ from typing import Optional
 import numpy as np
 
 from . import isa
-from ._lib import BpfLinkCreateArgs, BpfMapAttr, EbpfBatch, LaunchInfo, SysRecords, lib
+from ._lib import BpfLinkCreateArgs, BpfMapAttr, EbpfBatch, LaunchInfo, SysRecords, TraceLine, lib
 
 CTX_RAW, CTX_XDP, CTX_SYSCALL, CTX_SYSCALL_EXIT = 0, 1, 2, 3
 SYSCALL_RECORD, SYSCALL_RECORD_FULL, SYSCALL_RECORD_TIMED = 64, 96, 128  # include/bpftime_amd.h replay records
@@ -339,6 +339,24 @@ class VM:
     def set_step_limit(self, n: int) -> None:
         lib().bpftime_amd_set_step_limit(C.c_void_p(self.h), n)
 
+    def set_task(self, comm: Optional[bytes] = None, uid_gid: Optional[int] = None) -> None:
+        """What bpf_get_current_comm / bpf_get_current_uid_gid answer in this
+        VM's launches (bpftime_amd_vm_set_task); None leaves a part as it is.
+        comm: at most 63 bytes."""
+        if isinstance(comm, str):
+            comm = comm.encode()
+        u = C.c_uint64(uid_gid) if uid_gid is not None else None
+        if lib().bpftime_amd_vm_set_task(C.c_void_p(self.h), comm, C.byref(u) if u is not None else None):
+            raise EbpfError("set_task: comm longer than 63 bytes")
+
+    def get_task(self) -> tuple:
+        """(comm bytes up to its NUL, uid_gid)."""
+        buf = C.create_string_buffer(64)
+        u = C.c_uint64()
+        if lib().bpftime_amd_vm_get_task(C.c_void_p(self.h), buf, C.byref(u)):
+            raise EbpfError("get_task failed")
+        return buf.raw.split(b"\0", 1)[0], u.value
+
     def last_batch_ms(self) -> float:
         """Kernel time of this VM's last BATCH_TIMED batch (ms; -1 none)."""
         return lib().bpftime_amd_last_batch_ms(self.h)
@@ -381,6 +399,27 @@ class VM:
             self.close()
         except Exception:
             pass
+
+
+def enable_trace_printk(on: bool = True) -> bool:
+    """bpf_trace_printk on the device (bpftime_amd_enable_trace_printk): off
+    by default and after reset_runtime; VMs created while it is on have the
+    helper.  Returns the previous setting."""
+    return bool(lib().bpftime_amd_enable_trace_printk(1 if on else 0))
+
+
+def trace_read(max_lines: int = 1 << 16, text_cap: int = 1 << 22):
+    """bpf_trace_printk's lines since the last read (bpftime_amd_trace_read):
+    ([(unit, line bytes)] in ticket order, records lost to a full log).  None
+    when no program that calls the helper was loaded yet (no log)."""
+    lines = (TraceLine * max(max_lines, 1))()
+    text = C.create_string_buffer(max(text_cap, 1))
+    lost = C.c_uint64(0)
+    n = lib().bpftime_amd_trace_read(lines, max_lines, text, text_cap, C.byref(lost))
+    if n < 0:
+        return None
+    raw = text.raw
+    return [(lines[i].unit, raw[lines[i].text_off:lines[i].text_off + lines[i].text_len]) for i in range(n)], lost.value
 
 
 # ---------------------------------------------------------------------------

@@ -328,6 +328,42 @@ void bpftime_object_close(struct bpftime_object *obj);
  * count (-1: not a ring buffer).  Waits for queued batches first. */
 int64_t bpftime_amd_ringbuf_fetch(int fd, void *out, uint64_t cap, uint64_t *used);
 
+/* ---- task identity and bpf_trace_printk (Trace and task helpers) ----
+ * What bpf_get_current_comm (16) and bpf_get_current_uid_gid (15) answer in
+ * this VM's launches.  A VM that never set them answers as the reference
+ * does: the basename of the launching process's /proc/self/exe (at most 63
+ * bytes) and (getgid() << 32) | getgid().  `comm`: NUL-terminated, at most
+ * 63 bytes and the NUL (longer: -1, the VM unchanged); a NULL part stays as
+ * it is.  The getter copies 64 bytes of comm (zero from its NUL on). */
+int bpftime_amd_vm_set_task(struct ebpf_vm *vm, const char *comm, const uint64_t *uid_gid);
+int bpftime_amd_vm_get_task(const struct ebpf_vm *vm, char *comm, uint64_t *uid_gid);
+
+/* bpf_trace_printk (6) is off until the host enables it here (and off again
+ * after bpftime_amd_reset): while off it is no default helper
+ * (bpftime_amd_register_default_helpers, bpftime_amd_prog_instantiate, the
+ * syscall attachments) and a program that calls it is refused at load,
+ * naming the helper, as a helper without a device implementation is.  VMs
+ * created and programs loaded while it is on keep it.  Returns the previous
+ * setting (0 / 1). */
+int bpftime_amd_enable_trace_printk(int on);
+
+/* bpf_trace_printk (6) leaves a record in a device log (made when the first
+ * program that calls it is loaded; BPFTIME_AMD_TRACE_RECORDS records, default
+ * 65536, read then); this formats the records in ticket order, each line
+ * exactly what snprintf gives for its format and arguments, NUL-terminated at
+ * text + text_off.  Waits for queued batches first.  Delivers only lines that
+ * fit whole (max_lines, text_cap) and leaves the rest for the next call; adds
+ * the records lost to a full log since the last read to *lost.  Returns the
+ * lines delivered; -1 when no log exists.  `unit`: the calling unit's global
+ * index (a syscall replay: the record's). */
+struct bpftime_amd_trace_line {
+  uint64_t unit;
+  uint32_t text_off;
+  uint32_t text_len;
+};
+int64_t bpftime_amd_trace_read(struct bpftime_amd_trace_line *lines, uint64_t max_lines, char *text,
+                               uint64_t text_cap, uint64_t *lost);
+
 /* ---- syscall tracepoint dispatch (csrc/syscall_dispatch.cpp) ----
  * syscall_trace_attach_impl.cpp:18-95 over recorded syscalls in device memory.
  *
