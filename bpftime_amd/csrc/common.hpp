@@ -85,6 +85,7 @@ constexpr uint32_t MT_PERCPU_HASH = 5;
 constexpr uint32_t MT_PERCPU_ARRAY = 6;
 constexpr uint32_t MT_LRU_HASH = 9;
 constexpr uint32_t MT_LPM_TRIE = 11;
+constexpr uint32_t MT_ARRAY_OF_MAPS = 12;
 constexpr uint32_t MT_QUEUE = 22;
 constexpr uint32_t MT_STACK = 23;
 constexpr uint32_t MT_RINGBUF = 27;
@@ -124,6 +125,11 @@ constexpr uint32_t MT_BLOOM_FILTER = 30;
 //                  stride (value_size rounded up to 4), val_off = 128 (slot 0's
 //                  offset from data); the element with ticket t lives in slot
 //                  t % max_entries, count = tail - head (qs_* below)
+//   ARRAY_OF_MAPS  int32 map fd per index at data, stride 4, 0 = empty
+//                  (map_in_maps.hpp: an array of sizeof(int) values whatever
+//                  the attr's value_size says; DMap.value_size = 4); written
+//                  by the host only, a lookup yields the slot's fd as the map
+//                  "pointer" (dev_helpers.hpp helper_mapinmap)
 struct DMap {
   uint32_t type;
   uint32_t key_size;

@@ -1607,6 +1607,29 @@ __device__ __noinline__ uint64_t helper_trace(uint64_t fmt, uint64_t fmt_size, u
   return 0;
 }
 
+// ---------------------------------------------------------------------------
+// ARRAY_OF_MAPS (map_in_maps.hpp): the helpers 1 / 2 / 3 of a program on an
+// outer map (interp.hip call_helper sends them here; fd < kMaxFds, and the
+// calling lanes may name different outer maps).
+//    1 lookup: the slot's int as the inner map's "pointer", (void *)
+//      ((u_int64_t)map_id) (map_in_maps.hpp:25-30): sign-extended, an empty slot
+//      (0) is NULL.  The key is a u32 at a flat address of any alignment.  An
+//      out-of-range key answers NULL here; the reference dereferences
+//      array_map_impl::elem_lookup's nullptr (array_map.cpp:27-35).
+//    2 update, 3 delete: -EINVAL, "Map in maps only support update from
+//      syscall" (map_handler.cpp:365-369, :680-684); the slots stay as they are.
+// The fd a lookup yields is checked where it is used: every map helper
+// answers NULL / -1 for an fd >= kMaxFds (a negative slot is one) and for a
+// descriptor of type 0 (never created, or closed), touching no memory.
+// ---------------------------------------------------------------------------
+__device__ __noinline__ uint64_t helper_mapinmap(const DMap *maps, uint64_t fd, uint64_t key, uint32_t op) {
+  if (op != 1) return (uint64_t)(int64_t)-22;  // -EINVAL
+  const DMap m = load_dmap(maps, fd);
+  const uint32_t k = *(const u32u *)key;
+  if (k >= m.max_entries) return 0;
+  return (uint64_t)(int64_t) * (const volatile int32_t *)(m.data + 4ull * k);
+}
+
 __device__ uint64_t helper_lookup(const DMap *maps, uint64_t fd, uint64_t key, LaneEnv &env) {
   if (fd >= kMaxFds) return 0;
   const DMap m = load_dmap(maps, fd);

@@ -66,6 +66,9 @@ __device__ __forceinline__ uint64_t call_helper(uint32_t id, uint64_t a1, uint64
     const bool elem = id == 87 || id == 88 || id == 89;
     if (qs_type(mt) && (elem || id == 1 || id == 2 || id == 3))
       return helper_qs(maps, a1, id == 2 ? a3 : elem ? a2 : 0, id == 2 ? a4 : id == 87 ? a3 : 0, id, env.exact);
+    // an ARRAY_OF_MAPS: lookup yields the slot's fd, update / delete answer
+    // -EINVAL (87 / 88 / 89: -ENOTSUP below) -- dev_helpers.hpp helper_mapinmap
+    if (mt == MT_ARRAY_OF_MAPS && (id == 1 || id == 2 || id == 3)) return helper_mapinmap(maps, a1, a2, id);
     // bpf_map_push / pop / peek_elem, and a Bloom filter's bpf_map_update_elem:
     // a push of the value, the key ignored
     const bool upd = id == 2 && mt == MT_BLOOM_FILTER;

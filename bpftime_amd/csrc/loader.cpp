@@ -543,10 +543,12 @@ int load_program(const RawInsn *code, size_t n, const std::map<size_t, size_t> &
           if (!lddw.map_by_fd) { err = at + ", map_by_fd not defined"; return -EINVAL; }
           imm = lddw.map_by_fd((uint32_t)cur.imm);
           {  // a Bloom filter named by fd: helper 2 on it is a push; a QUEUE /
-             // STACK: helpers 1 / 2 / 3 are peek / push / pop
+             // STACK: helpers 1 / 2 / 3 are peek / push / pop; an
+             // ARRAY_OF_MAPS: helper 1 yields a map fd
             Runtime &r = rt();
             if (imm < kMaxFds && r.kind[imm] == HKind::MAP &&
-                (r.maps[imm].type == MT_BLOOM_FILTER || qs_type(r.maps[imm].type)))
+                (r.maps[imm].type == MT_BLOOM_FILTER || qs_type(r.maps[imm].type) ||
+                 r.maps[imm].type == MT_ARRAY_OF_MAPS))
               out.bloom = true;
           }
           break;
@@ -932,8 +934,12 @@ static bool pointer_kinds(const std::vector<DInsn> &p, const std::vector<uint8_t
         // (a copy helper's destination of run-time length inside the ctx may
         // reach its packet pointers)
         if (writes_r1_helper(d.hi) && st[1].kind == P_CTX) ctx_written = true;
-        // (not of a QUEUE / STACK: the slot a peek returns is no element of a keyed value array)
-        st[0] = (d.hi == 1 && m.kind == P_MAPFD && map_rec(m.id) && !qs_type(map_rec(m.id)->type))
+        // (not of a QUEUE / STACK: the slot a peek returns is no element of a keyed value array;
+        // not of an ARRAY_OF_MAPS: the result is a map handle, no pointer into
+        // the outer map's storage -- every call through it has r1 unresolved,
+        // and what it reaches counts against every map)
+        st[0] = (d.hi == 1 && m.kind == P_MAPFD && map_rec(m.id) && !qs_type(map_rec(m.id)->type) &&
+                 map_rec(m.id)->type != MT_ARRAY_OF_MAPS)
                     ? PVal{P_MVNULL, 0, m.id}
                     : kOther;
         break;
@@ -1243,6 +1249,10 @@ static void lpm_write_sites(const std::vector<DInsn> &p, const std::vector<uint8
     const uint64_t v = (uint64_t)(uint32_t)p[i].imm | ((uint64_t)(uint32_t)p[i].hi << 32);
     const MapRec *m = v < kMaxFds ? map_rec((int64_t)v) : nullptr;
     if (m && m->type == MT_LPM_TRIE) named.push_back((int32_t)v);
+    // (the ARRAY_OF_MAPS maps the program names: FastForm::outer_maps)
+    if (m && m->type == MT_ARRAY_OF_MAPS &&
+        std::find(out.outer_maps.begin(), out.outer_maps.end(), (int32_t)v) == out.outer_maps.end())
+      out.outer_maps.push_back((int32_t)v);
   }
   out.names_lpm = !named.empty();
   auto add = [&](uint32_t h, int32_t fd) {

@@ -77,6 +77,10 @@ struct FastForm {
     bool flags0;
   };
   std::vector<QsSite> qs_sites;
+  // the ARRAY_OF_MAPS maps the program names in an lddw.  The inner maps a
+  // lookup on one yields are named by no lddw: before a launch the host walks
+  // the slots of these maps (vm_api.cpp inner_launch_check)
+  std::vector<int32_t> outer_maps;
   // a store may reach the unit r1 points to at entry (the pointer kinds
   // cannot place every store on the stack, a map value or a constant)
   bool stores_unit = true;
@@ -95,7 +99,7 @@ struct LoadOut {
   bool big_stack = false;    // 512-B scratch stack
   uint32_t fused_rmw = 0;
   uint32_t comb_entries = 0;  // per-block LDS combining entries (0 = none needed)
-  bool bloom = false;         // calls bpf_map_push / pop / peek_elem or names a BLOOM_FILTER / QUEUE / STACK: scratch-stack kernels only
+  bool bloom = false;         // calls bpf_map_push / pop / peek_elem or names a BLOOM_FILTER / QUEUE / STACK / ARRAY_OF_MAPS: scratch-stack kernels only
   bool trace_printk = false;  // calls bpf_trace_printk: the runtime's trace log must exist before a launch
   bool may_delete = false;    // calls map_delete_elem: hash lookup indexes stop being valid
   bool tail_call = false;     // calls bpf_tail_call: linked with the prog arrays' targets at launch

@@ -4,6 +4,7 @@
 // runtime/src/handler/map_handler.cpp:109-330 over
 //   array_map.cpp:19-81, fix_hash_map.cpp:16-84 + bpftime_hash_map.hpp,
 //   per_cpu_array_map.cpp:97-145, per_cpu_hash_map.cpp:141-216,
+//   map_in_maps.hpp (map_arrmaps.cpp),
 // with storage in one device arena (HBM) whose layout is described by the
 // DMap records the interpreter reads (csrc/common.hpp).  Host-side ops copy
 // the touched slots over PCIe: they are control-plane operations and must not
@@ -39,6 +40,7 @@ const MapOps *map_ops(uint32_t type) {
     case MT_BLOOM_FILTER: return &kBloomFilterOps;
     case MT_QUEUE: return &kQueueOps;
     case MT_STACK: return &kStackOps;
+    case MT_ARRAY_OF_MAPS: return &kArrayOfMapsOps;
   }
   return nullptr;
 }
@@ -206,6 +208,10 @@ uint64_t bpftime_amd_map_val(uint64_t map_ptr) {
       return m->max_entries ? m->d.data : 0;
     case MT_PERCPU_ARRAY:
       return m->max_entries ? m->d.data : 0;  // cpu 0's slot of key 0
+    case MT_ARRAY_OF_MAPS:
+      // the reference looks key 0 up (bpftime_shm.cpp:654-676), which for
+      // this type is slot 0's map id as a pointer (map_in_maps.hpp:25-30)
+      return m->max_entries ? (uint64_t)(int64_t)m->inner_slots[0] : 0;
     default: {
       uint8_t key[512];
       if (m->key_size > sizeof(key) || bpftime_map_get_next_key(fd, nullptr, key) < 0) {
@@ -236,7 +242,10 @@ int bpftime_amd_map_restore(int fd, const void *in, uint64_t bytes) {
   MapRec *m = map_of(fd);
   if (!m || bytes > m->bytes) return -1;
   ix_invalidate(fd);
+  // (an ARRAY_OF_MAPS: no launch may be reading the slots, map_arrmaps.cpp)
+  if (m->type == MT_ARRAY_OF_MAPS && hipDeviceSynchronize() != hipSuccess) return -1;
   if (hipMemcpy((void *)m->d.data, in, bytes, hipMemcpyHostToDevice) != hipSuccess) return -1;
+  if (m->type == MT_ARRAY_OF_MAPS) return arrmaps_pull(*m);
   if (m->d.count_addr) {
     uint64_t c = 0;
     for (uint64_t i = 0; i < m->d.nbuckets && (i + 1) * m->d.slot_size <= bytes; i++) {

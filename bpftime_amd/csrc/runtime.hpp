@@ -36,6 +36,10 @@ struct MapRec {
   // every host op on the trie and every launch naming a trie reports it
   // (ENOMEM) until bpftime_amd_map_ack_error
   bool lpm_pool_out = false;
+  // ARRAY_OF_MAPS: the host's copy of the slots (map_arrmaps.cpp keeps it equal
+  // to the arena's).  The launch walk (vm_api.cpp inner_launch_check) reads the
+  // inner fds here, never from device memory
+  std::vector<int32_t> inner_slots;
   // BPF_MAP_CREATE attributes as given (BPF_OBJ_GET_INFO_BY_FD reports them)
   uint32_t ifindex = 0, btf_vmlinux_value_type_id = 0, btf_id = 0, btf_key_type_id = 0, btf_value_type_id = 0;
   uint64_t map_extra = 0;

@@ -36,6 +36,8 @@ extern "C" long bpftime_amd_handle_sysbpf(int cmd, void *attr_, uint32_t size) {
       a.btf_id = attr->btf_fd;
       a.btf_key_type_id = attr->btf_key_type_id;
       a.btf_value_type_id = attr->btf_value_type_id;
+      // (BPF_MAP_TYPE_ARRAY_OF_MAPS: attr->inner_map_fd is not read, as
+      // bpftime_shm_internal.cpp:889 ignores it -- bpf_map_attr has no such field)
       // map_extra follows btf_vmlinux_value_type_id in the kernel ABI (newer
       // than this image's linux/bpf.h): read when the caller's attr has it
       const size_t xoff = (offsetof(union bpf_attr, btf_vmlinux_value_type_id) + 4 + 7) & ~(size_t)7;

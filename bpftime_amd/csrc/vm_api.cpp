@@ -148,6 +148,49 @@ static bool qs_launch_fence(bool adds, bool takes) {
   return true;
 }
 
+// ARRAY_OF_MAPS: the maps a launch of the program form `f` reaches without
+// naming them in an lddw -- whatever the slots of the outer maps it names
+// (loader.cpp, FastForm::outer_maps) hold.  The walk reads the host mirror of
+// the slots (MapRec::inner_slots), never device memory; a host write of a slot
+// waits for the device first (map_arrmaps.cpp), so the mirror is what the
+// kernel will read.  It runs before any kernel is launched.
+//
+// Inner ARRAY, PERCPU_ARRAY, HASH and PERCPU_HASH maps are accepted in every
+// batch mode.  Everything a launch prepares for them is prepared for every
+// such map of the runtime, named or not: the hash lookup indexes (Runtime::
+// prepare_ix rebuilds every stale one and, for a program that calls
+// map_delete_elem -- LoadOut::may_delete is a property of the program, not of
+// a map -- invalidates them all), the element counts and index inserts (the
+// device's own, dev_helpers.hpp hash_find), the host views (host_views_push /
+// _pull) and the deleter / lookup-cache fences (keyed on the program).  The
+// other types have per-launch work keyed on the maps a program names (LPM
+// launch lock, replica upload and flat table; QUEUE / STACK access kinds and
+// fences; ring staging; prog-array linking; the Bloom and LRU helpers'
+// call-site routing), which an unnamed map would miss: a slot that holds one
+// refuses the launch.  A slot that names no live map (0, garbage, a closed
+// fd) is fine: the device answers NULL / -1 for it.
+static bool inner_launch_check(const FastForm &f, std::string &error) {
+  if (f.outer_maps.empty()) return true;
+  Runtime &r = rt();
+  std::lock_guard<std::mutex> g(r.mu);
+  for (const int32_t ofd : f.outer_maps) {
+    if (ofd < 0 || ofd >= (int32_t)kMaxFds || r.kind[ofd] != HKind::MAP || r.maps[ofd].type != MT_ARRAY_OF_MAPS)
+      continue;  // closed since the load: the device answers NULL
+    const std::vector<int32_t> &slots = r.maps[ofd].inner_slots;
+    for (size_t i = 0; i < slots.size(); i++) {
+      const int32_t ifd = slots[i];
+      if (ifd < 0 || ifd >= (int32_t)kMaxFds || r.kind[ifd] != HKind::MAP) continue;
+      const uint32_t t = r.maps[ifd].type;
+      if (t == MT_ARRAY || t == MT_PERCPU_ARRAY || t == MT_HASH || t == MT_PERCPU_HASH) continue;
+      error = "ARRAY_OF_MAPS map fd " + std::to_string(ofd) + " slot " + std::to_string(i) + " holds map fd " +
+              std::to_string(ifd) + " of type " + std::to_string(t) +
+              ": inner maps must be ARRAY, PERCPU_ARRAY, HASH or PERCPU_HASH";
+      return false;
+    }
+  }
+  return true;
+}
+
 extern "C" int bpftime_amd_occupancy(uint32_t kind, bool big_stack, size_t dyn_lds, bool gregs, uint32_t block,
                                     bool image);
 extern "C" size_t bpftime_amd_static_lds_image(uint32_t kind, bool big_stack, bool gregs, uint32_t block, bool image);
@@ -735,6 +778,8 @@ int Mi355xVm::exec_batch(const ebpf_batch *b) {
     return -1;
   }
   Image &im = *imp;
+  // ARRAY_OF_MAPS: the inner maps the slots name, before anything is queued
+  if (!inner_launch_check(kind == CTX_XDP ? im.fx : im.fr, error)) return -1;
   // the unwind helper as the device knows helpers (bpftime ids): the
   // registration that was given ubpf id unwind_idx
   int32_t unwind_helper = -1;
@@ -1462,6 +1507,10 @@ int64_t seq_dispatch(const std::vector<SeqAttach> &progs, const SysLayout &lay, 
     }
     may_delete |= im->prog.may_delete;
     names_lpm |= im->fr.names_lpm;
+    {  // ARRAY_OF_MAPS: the inner maps its slots name (as exec_batch)
+      std::string ie;
+      if (!inner_launch_check(im->fr, ie)) return fail(ie);
+    }
     {  // QUEUE / STACK maps: lanes in thread order are not record order across threads
       std::string qe;
       bool touches_add = false, touches_take = false;

@@ -94,6 +94,7 @@ BPF_MAP_TYPE_PERCPU_HASH = 5
 BPF_MAP_TYPE_PERCPU_ARRAY = 6
 BPF_MAP_TYPE_LRU_HASH = 9
 BPF_MAP_TYPE_LPM_TRIE = 11
+BPF_MAP_TYPE_ARRAY_OF_MAPS = 12
 BPF_MAP_TYPE_RINGBUF = 27
 BPF_MAP_TYPE_QUEUE = 22
 BPF_MAP_TYPE_STACK = 23

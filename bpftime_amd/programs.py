@@ -863,3 +863,41 @@ def sys_enter_tracer(comm_fd: int, counts_fd: int) -> bytes:
     a.label("add").mov64(2, 1).atomic(8, ATOMIC_ADD, 0, 0, "r2")
     a.label("out").mov64(0, 0).exit()
     return a.assemble()
+
+
+# ---- BPF_MAP_TYPE_ARRAY_OF_MAPS (map-in-map lookups) -------------------------
+def tenant_counter(outer_fd: int) -> bytes:
+    """Per-tenant counters: the packet's byte 0 (& 3) picks the tenant's table
+    in the ARRAY_OF_MAPS, the u32 at packet offset 4 the counter in it; adds 1
+    to that u64.  XDP_DROP when the tenant has no table (an empty slot) or the
+    table has no such counter, else XDP_PASS.  The host swaps a tenant's whole
+    table by rewriting one slot.  Both keys are read in place from the packet
+    (the outer index is written back over byte 0..3 first).
+    outer_fd: ARRAY_OF_MAPS of >= 4 slots over ARRAY maps, key 4, value 8."""
+    a = Asm()
+    a.ldx(8, 6, 1, 0)                     # r6 = data
+    a.ldx(4, 2, 6, 0).alu64("and", 2, 3).stx(4, 6, 0, "r2")
+    a.ld_map_fd(1, outer_fd).mov64(2, "r6").call(BPF_FUNC_map_lookup_elem)
+    a.mov64(1, "r0").mov64(0, XDP_DROP).jmp("jeq", 1, 0, "out")
+    a.mov64(2, "r6").add64(2, 4).call(BPF_FUNC_map_lookup_elem)
+    a.mov64(1, "r0").mov64(0, XDP_DROP).jmp("jeq", 1, 0, "out")
+    a.mov64(2, 1).atomic(8, ATOMIC_ADD, 1, 0, "r2")
+    a.mov64(0, XDP_PASS)
+    a.label("out").exit()
+    return a.assemble()
+
+
+def tenant_counter_bound(inner_fd: int) -> bytes:
+    """tenant_counter with one tenant's table bound by an lddw instead of
+    looked up in an outer map: the same packet writes, the same second lookup
+    and add."""
+    a = Asm()
+    a.ldx(8, 6, 1, 0)
+    a.ldx(4, 2, 6, 0).alu64("and", 2, 3).stx(4, 6, 0, "r2")
+    a.ld_map_fd(1, inner_fd)
+    a.mov64(2, "r6").add64(2, 4).call(BPF_FUNC_map_lookup_elem)
+    a.mov64(1, "r0").mov64(0, XDP_DROP).jmp("jeq", 1, 0, "out")
+    a.mov64(2, 1).atomic(8, ATOMIC_ADD, 1, 0, "r2")
+    a.mov64(0, XDP_PASS)
+    a.label("out").exit()
+    return a.assemble()

@@ -182,6 +182,17 @@ class Map:
     def count(self) -> int:
         return lib().bpftime_amd_map_count(self.fd)
 
+    # BPF_MAP_TYPE_ARRAY_OF_MAPS (map_in_maps.hpp)
+    def set_inner(self, index: int, inner, flags: int = 0) -> int:
+        """ARRAY_OF_MAPS: store the map `inner` (a Map or a raw int: the slots
+        are untyped) in slot `index`; what bpftime_map_update_elem returns."""
+        fd = inner.fd if isinstance(inner, Map) else int(inner)
+        return self.update(struct.pack("<I", index), struct.pack("<i", fd), flags)
+
+    def inner_fds(self) -> list:
+        """ARRAY_OF_MAPS: the int each slot holds (0: empty), from a snapshot."""
+        return [int(x) for x in self.snapshot().view(np.int32)]
+
     # BPF_MAP_TYPE_QUEUE / _STACK / _BLOOM_FILTER (bpftime_shm.cpp:168-200)
     def push(self, value: bytes, flags: int = 0) -> int:
         v = C.create_string_buffer(bytes(value), len(value))

@@ -56,7 +56,22 @@ struct bpf_link_create_args {
  * fix-size hash, map_handler.cpp:54-58), ARRAY (2), PROG_ARRAY (3, prog
  * fds, prog_array.cpp; the targets of bpf_tail_call, linked into the caller's
  * image at launch), PERCPU_HASH (5), PERCPU_ARRAY (6), LRU_HASH (9),
- * LPM_TRIE (11), QUEUE (22) and STACK (23: value_size > 0 and max_entries >
+ * LPM_TRIE (11), ARRAY_OF_MAPS (12, map_in_maps.hpp: max_entries int32 slots
+ * whatever value_size says, each the fd of an inner map or 0; there is no
+ * inner_map_fd, so a slot takes any int.  The host writes slots with
+ * bpftime_map_update_elem (the array map's rules: EEXIST for BPF_NOEXIST,
+ * E2BIG past the end; it waits for running batches first), reads a 4-byte
+ * copy with bpftime_map_lookup_elem (NULL / ENOENT past the end -- the
+ * reference dereferences a null pointer there and returns the id as a
+ * pointer), delete is EINVAL, get_next_key the array's.  A program's
+ * bpf_map_lookup_elem on it yields the slot's fd as the inner map's handle
+ * (NULL for an empty slot or a key past the end) for its next map helper
+ * call; its update / delete answer -EINVAL.  A slot that names no live map
+ * makes those calls answer NULL / -1.  Inner maps must be ARRAY,
+ * PERCPU_ARRAY, HASH or PERCPU_HASH: a launch of a program that names an
+ * outer map whose slots hold a live map of any other type is refused before
+ * any kernel runs, with an error naming the outer fd, slot, inner fd and
+ * type), QUEUE (22) and STACK (23: value_size > 0 and max_entries >
  * 0, the key size is not looked at; queue.cpp, stack.cpp), RINGBUF (27),
  * BLOOM_FILTER (30: key_size 0, nr_hashes = map_extra & 0xF with 0 meaning 5,
  * bloom_filter.cpp).  Returns fd or -1 (errno set). */
