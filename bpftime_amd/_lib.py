@@ -174,6 +174,9 @@ SIGNATURES = [
     ("bpftime_perf_event_disable", C.c_int, [C.c_int]),
     ("bpftime_amd_perf_event_record", C.c_int, [C.c_int, C.POINTER(PerfEvent)]),
     ("bpftime_amd_perf_event_get", C.c_int, [C.c_int, C.POINTER(PerfEvent)]),
+    ("bpftime_amd_perf_event_mmap", C.c_int, [C.c_int, C.c_uint64]),
+    ("bpftime_amd_perf_event_fetch", C.c_int64, [C.c_int, C.c_void_p, C.c_uint64, u64p]),
+    ("bpftime_amd_perf_event_ring_state", C.c_int, [C.c_int, u64p, u64p, u64p]),
     ("bpftime_amd_link_perf", C.c_int, [C.c_int, C.c_int, C.c_int]),
     ("bpftime_amd_link_attached", C.c_int, [C.c_int]),
     ("bpftime_amd_set_tracefs_events", C.c_int, [C.c_char_p]),

@@ -81,6 +81,7 @@ static_assert(sizeof(DInsn) == 16, "DInsn must be 16 bytes");
 constexpr uint32_t MT_HASH = 1;
 constexpr uint32_t MT_ARRAY = 2;
 constexpr uint32_t MT_PROG_ARRAY = 3;
+constexpr uint32_t MT_PERF_EVENT_ARRAY = 4;
 constexpr uint32_t MT_PERCPU_HASH = 5;
 constexpr uint32_t MT_PERCPU_ARRAY = 6;
 constexpr uint32_t MT_LRU_HASH = 9;
@@ -130,6 +131,10 @@ constexpr uint32_t MT_BLOOM_FILTER = 30;
 //                  the attr's value_size says; DMap.value_size = 4); written
 //                  by the host only, a lookup yields the slot's fd as the map
 //                  "pointer" (dev_helpers.hpp helper_mapinmap)
+//   PERF_EVENT_ARRAY  int32 perf event fd per index at data, stride 4, -1 =
+//                  empty (perf_event_array_map.cpp:14-26); written by the host
+//                  only.  bpf_perf_event_output reads the slot of the lane's
+//                  CPU and finds the fd's ring in the perf table (DPerf below)
 struct DMap {
   uint32_t type;
   uint32_t key_size;
@@ -146,6 +151,27 @@ struct DMap {
   uint64_t ix;          // device address of the u32 lookup index, 0 = not valid (LPM_TRIE: its flat table)
 };
 static_assert(sizeof(DMap) == 64, "DMap must be 64 bytes");
+
+// The device's perf table: one record per fd, kMaxFds of them behind the map
+// table (Runtime::d_maptab + kMaxFds), written by the host only
+// (runtime.cpp push_perf).  `soft`: the fd is a software perf event, the only
+// kind bpf_perf_event_output writes to.  Its ring, once the host gave it one
+// (bpftime_amd_perf_event_mmap): u64 data_head at ring, u64 data_tail at ring
+// + 128 (a line each, as the RINGBUF positions), data_bytes (a power of two)
+// record bytes at ring + 256.  data_bytes 0: no ring yet, every output is
+// dropped (software_perf_event_buffer::mmap_size() == 0,
+// perf_event_handler.cpp:318).
+struct DPerf {
+  uint64_t ring;
+  uint64_t data_bytes;
+  uint32_t soft;
+  uint32_t pad[3];
+};
+static_assert(sizeof(DPerf) == 32, "DPerf must be 32 bytes");
+constexpr uint32_t kPerfRingHdr = 256;     // head line + tail line
+constexpr uint32_t kPerfTailOff = 128;
+constexpr uint32_t kPerfRecHdr = 12;       // perf_event_header (8) + u32 size: perf_sample_raw
+constexpr uint64_t kPerfMaxData = 65535 - kPerfRecHdr - 7;  // output_data's E2BIG bound (:359-363)
 
 // QUEUE / STACK (runtime/src/bpf_map/userspace/queue.cpp, stack.cpp).  Push
 // writes the slot of ticket `tail`; a queue pops at `head`, a stack at `tail -

@@ -1630,6 +1630,136 @@ __device__ __noinline__ uint64_t helper_mapinmap(const DMap *maps, uint64_t fd, 
   return (uint64_t)(int64_t) * (const volatile int32_t *)(m.data + 4ull * k);
 }
 
+// ---------------------------------------------------------------------------
+// bpf_perf_event_output(ctx, map, flags, data, size) (25): bpf_helper.cpp:506-566
+// over software_perf_event_buffer::output_data / append_record_parts
+// (perf_event_handler.cpp:355-376, :306-353).  ctx and flags are not read (the
+// reference reads neither, BPF_F_CURRENT_CPU included).  Per lane, in order:
+//   the map must be a live PERF_EVENT_ARRAY and cpu < max_entries, else -1;
+//   the slot of `cpu` must name a software perf event (common.hpp DPerf::soft;
+//     an empty slot is -1, an fd >= kMaxFds), else -1;
+//   size > kPerfMaxData (unsigned): -1 (E2BIG there);
+//   [data, data + size) must be a range mem_guard.hpp accepts, else -EFAULT
+//     (the reference copies unchecked; a size of 0 reads nothing);
+//   record_size = (12 + size + 7) & ~7.  No ring yet, record_size > data_bytes,
+//     or data_bytes - (head - tail) <= record_size (one byte stays free): the
+//     record is dropped and the call answers 0, as output_data ignores
+//     append_record_parts' result;
+//   else the record -- u32 type 9 (PERF_RECORD_SAMPLE), u16 misc 0, u16
+//     record_size, u32 record_size - 12, the data; the padding is not written
+//     -- lies at head & (data_bytes - 1), wrapping at the ring's end, head moves
+//     on by record_size, and the call answers 0.
+// Many lanes, waves and blocks produce into one ring; its one consumer
+// (bpftime_amd_perf_event_fetch) synchronizes the device first, so data_tail
+// stands still while a launch runs and no record needs a BUSY mark.  The
+// calling lanes are grouped by ring (each lane may name another map, slot or
+// ring).  One lane of a group claims for all of it: it loads head, decides in
+// lane order which records fit -- each against the room left once the taken
+// ones before it lie there, which is what the lanes calling one after another
+// would get -- and moves head past the taken ones with one agent-scope
+// compare-and-swap.  A claim that takes nothing does not touch head, so the
+// stream between tail and head always parses.  A lost swap means another wave
+// moved head by at least 16 bytes, and head never passes tail + data_bytes -
+// 1: the retries are bounded by the ring's size, and no lane waits for
+// another.  An ORDERED batch's single lane runs the same claim.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t readlane32(uint32_t v, uint32_t lane) {
+  return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)lane);
+}
+__device__ __forceinline__ uint64_t readlane64u(uint64_t v, uint32_t lane) {
+  return (uint64_t)readlane32((uint32_t)v, lane) | ((uint64_t)readlane32((uint32_t)(v >> 32), lane) << 32);
+}
+
+__device__ __noinline__ uint64_t helper_perf_output(const DMap *maps, uint64_t map, uint64_t data, uint64_t size,
+                                                    uint32_t cpu, Win win, MemLane ml) {
+  constexpr uint64_t kFail = ~0ull;
+  // the slot's fd (kMaxFds: none), then the fd's perf record with one
+  // unconditional load, so that what the claim reads across lanes (ring,
+  // data_bytes, rs) comes from straight-line selects
+  uint32_t pfd = kMaxFds;
+  if (map < kMaxFds) {
+    const DMap m = maps[map];
+    if (m.type == MT_PERF_EVENT_ARRAY && cpu < m.max_entries)
+      pfd = (uint32_t) * (const volatile int32_t *)(m.data + 4ull * cpu);
+  }
+  const bool have = pfd < kMaxFds;
+  const volatile DPerf *pt = (const volatile DPerf *)(maps + kMaxFds) + (have ? pfd : 0);
+  const uint64_t pe_ring = pt->ring, pe_bytes = pt->data_bytes;
+  const uint32_t pe_soft = pt->soft;
+  const bool sized = have && pe_soft != 0 && size <= kPerfMaxData;
+  const bool range = sized && (size == 0 || mem_range_ok(win, ml, data, size));
+  const uint64_t ret = !sized ? kFail : !range ? kEfault : 0;
+  const uint32_t rs = sized ? (uint32_t)((kPerfRecHdr + size + 7) & ~7ull) : 0;
+  const bool want = range && pe_ring != 0 && pe_bytes != 0 && rs <= pe_bytes;
+  const uint64_t ring = want ? pe_ring : 0, db = want ? pe_bytes : 0;
+  const uint32_t me = __lane_id();
+  uint64_t pending = __ballot(want);
+  uint64_t off = 0;
+  bool took = false;
+  while (pending) {
+    const uint32_t leader = (uint32_t)__builtin_ctzll(pending);
+    const uint64_t ring0 = readlane64u(ring, leader), db0 = readlane64u(db, leader);
+    const bool mine = want && ring == ring0;
+    const uint64_t grp = __ballot(mine);
+    pending &= ~grp;
+    // tail: constant while the launch runs
+    uint64_t head = 0, tail = 0;
+    if (me == leader) {
+      head = __hip_atomic_load(G64(ring0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      tail = __hip_atomic_load(G64(ring0 + kPerfTailOff), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    tail = readlane64u(tail, leader);
+    const uint64_t bound = db0 / 16 + 2;
+    uint32_t backoff = 1;
+    for (uint64_t tries = 0; tries < bound; tries++) {
+      const uint64_t h = readlane64u(head, leader);
+      uint64_t cur = h, taken = 0, myoff = 0;
+      // (head < tail or a ring as full as it gets: an invalid state drops, :325-330)
+      const bool valid = h >= tail && h - tail < db0;
+      for (uint64_t b = valid ? grp : 0; b; b &= b - 1) {
+        const uint32_t l = (uint32_t)__builtin_ctzll(b);
+        const uint64_t x = readlane32(rs, l);
+        if (db0 - (cur - tail) > x) {
+          taken |= 1ull << l;
+          myoff = l == me ? cur : myoff;
+          cur += x;
+        }
+      }
+      if (!taken) break;  // nothing fits: head stays
+      uint32_t won = 0;
+      if (me == leader) {
+        unsigned long long e = h;
+        won = __hip_atomic_compare_exchange_strong(G64(ring0), &e, cur, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                   __HIP_MEMORY_SCOPE_AGENT)
+                  ? 1
+                  : 0;
+        head = e;  // (lost: the head another wave set)
+      }
+      if (readlane32(won, leader)) {
+        if (mine && ((taken >> me) & 1)) {
+          took = true;
+          off = myoff;
+        }
+        break;
+      }
+      // lost to another wave: back off (thousands of waves share this word)
+      for (uint32_t i = 0; i < backoff; i++) __builtin_amdgcn_s_sleep(2);
+      backoff = backoff < 64 ? 2 * backoff : 64;
+    }
+  }
+  if (took) {
+    const uint64_t mask = db - 1, base = ring + kPerfRingHdr;
+    // (records are 8-aligned in a ring of a power of two >= 64: neither word splits)
+    *(volatile uint64_t *)(base + (off & mask)) = 9ull | ((uint64_t)rs << 48);
+    *(volatile uint32_t *)(base + ((off + 8) & mask)) = rs - kPerfRecHdr;
+    const uint64_t at = (off + kPerfRecHdr) & mask;
+    const uint64_t first = size <= db - at ? size : db - at;
+    mem_copy(base + at, data, first);
+    if (size > first) mem_copy(base, data + first, size - first);
+  }
+  return ret;
+}
+
 __device__ uint64_t helper_lookup(const DMap *maps, uint64_t fd, uint64_t key, LaneEnv &env) {
   if (fd >= kMaxFds) return 0;
   const DMap m = load_dmap(maps, fd);

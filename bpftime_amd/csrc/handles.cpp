@@ -2,7 +2,10 @@
 #include <errno.h>
 
 #include "../../include/bpftime_amd.h"
+#include "perf_ring.hpp"
 #include "runtime.hpp"
+
+#include <string.h>
 
 using namespace bpftime_amd;
 
@@ -82,6 +85,7 @@ static int perf_create(int fd, const PerfRec &p) {
   if (fd < 0) return -1;
   r.perfs[fd] = p;
   r.kind[fd] = HKind::PERF;
+  r.perf_dirty = true;  // (the device's perf table, runtime.cpp push_perfs)
   return fd;
 }
 
@@ -155,6 +159,112 @@ int bpftime_amd_perf_event_get(int fd, struct bpftime_amd_perf_event *e) {
   e->sample_type = p.sample_type;
   e->config = p.config;
   return 0;
+}
+
+// ---- the ring of a software perf event --------------------------------------
+// software_perf_event_buffer (perf_event_handler.cpp:235-450): a header page
+// and mmap_size() data bytes, sized when the consumer mmaps the perf fd
+// (ensure_mmap_buffer, :264-293); before that every output is dropped.  Here
+// the ring lives in the device arena (common.hpp DPerf): the positions on a
+// line each, then the data bytes.  It is made once: the reference grows the
+// buffer on a larger mmap, the arena only ever hands out fresh bytes, so a
+// second size is refused.
+static PerfRec *soft_perf(Runtime &r, int fd) {
+  if (fd < 0 || fd >= (int)kMaxFds || r.kind[fd] != HKind::PERF || r.perfs[fd].type != 1) {
+    errno = EINVAL;
+    return nullptr;
+  }
+  return &r.perfs[fd];
+}
+
+int bpftime_amd_perf_event_mmap(int perf_fd, uint64_t data_bytes) {
+  Runtime &r = rt();
+  std::lock_guard<std::mutex> g(r.mu);
+  PerfRec *p = soft_perf(r, perf_fd);
+  if (!p) {
+    set_error("fd " + std::to_string(perf_fd) + " is not a software perf event");
+    return -1;
+  }
+  if (data_bytes < 64 || (data_bytes & (data_bytes - 1))) {
+    errno = EINVAL;
+    set_error("Data size of a perf event buffer must be power of 2 (at least 64)");
+    return -1;
+  }
+  if (p->ring) {
+    if (p->ring_bytes == data_bytes) return 0;
+    errno = EINVAL;
+    set_error("perf event " + std::to_string(perf_fd) + " has a ring of " + std::to_string(p->ring_bytes) +
+              " bytes: a ring cannot be resized");
+    return -1;
+  }
+  if (r.ensure_device() < 0) return -1;
+  const uint64_t base = r.arena_alloc(kPerfRingHdr + data_bytes);
+  if (!base) {
+    errno = ENOMEM;
+    set_error("map arena exhausted (BPFTIME_AMD_ARENA_MB)");
+    return -1;
+  }
+  if (hipMemset((void *)base, 0, kPerfRingHdr + data_bytes) != hipSuccess) return -1;
+  p->ring = base;
+  p->ring_bytes = data_bytes;
+  r.perf_dirty = true;
+  return 0;
+}
+
+int bpftime_amd_perf_event_ring_state(int perf_fd, uint64_t *head, uint64_t *tail, uint64_t *data_bytes) {
+  Runtime &r = rt();
+  uint64_t ring, bytes;
+  {
+    std::lock_guard<std::mutex> g(r.mu);
+    PerfRec *p = soft_perf(r, perf_fd);
+    if (!p) return -1;
+    ring = p->ring;
+    bytes = p->ring_bytes;
+  }
+  uint64_t h = 0, t = 0;
+  if (ring) {
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpy(&h, (void *)ring, 8, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(&t, (void *)(ring + kPerfTailOff), 8, hipMemcpyDeviceToHost) != hipSuccess)
+      return -1;
+  }
+  if (head) *head = h;
+  if (tail) *tail = t;
+  if (data_bytes) *data_bytes = bytes;
+  return 0;
+}
+
+// The consumer: the producers of queued batches finish first, as
+// bpftime_amd_ringbuf_fetch has it; the walk is perf_ring.hpp's.
+int64_t bpftime_amd_perf_event_fetch(int perf_fd, void *out, uint64_t cap, uint64_t *used) {
+  Runtime &r = rt();
+  if (used) *used = 0;
+  uint64_t ring, bytes;
+  {
+    std::lock_guard<std::mutex> g(r.mu);
+    PerfRec *p = soft_perf(r, perf_fd);
+    if (!p) return -1;
+    ring = p->ring;
+    bytes = p->ring_bytes;
+  }
+  if (!ring) return 0;
+  if (!out && cap) {
+    errno = EINVAL;
+    return -1;
+  }
+  if (hipDeviceSynchronize() != hipSuccess) return -1;
+  uint64_t head, tail;
+  if (hipMemcpy(&head, (void *)ring, 8, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(&tail, (void *)(ring + kPerfTailOff), 8, hipMemcpyDeviceToHost) != hipSuccess)
+    return -1;
+  if (head == tail) return 0;
+  std::vector<uint8_t> data(bytes);
+  if (hipMemcpy(data.data(), (void *)(ring + kPerfRingHdr), bytes, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  uint64_t u = 0;
+  const int64_t n = perf_ring_walk(data.data(), bytes, head, &tail, (uint8_t *)out, cap, &u);
+  if (hipMemcpy((void *)(ring + kPerfTailOff), &tail, 8, hipMemcpyHostToDevice) != hipSuccess) return -1;
+  if (used) *used = u;
+  return n;
 }
 
 static int perf_enable(int fd, bool on) {  // :317-337

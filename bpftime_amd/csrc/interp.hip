@@ -59,6 +59,9 @@ __device__ __forceinline__ uint64_t call_helper(uint32_t id, uint64_t a1, uint64
     // and ctx extents -- dev_helpers.hpp helper_mem
     if (id == 4 || id == 112 || id == 113 || id == 45 || id == 114 || id == 115 || id == 182 || id == 36)
       return helper_mem(id, a1, a2, a3, win, ml);
+    // bpf_perf_event_output(ctx, map, flags, data, size): the map is r2, ctx
+    // and flags are not read -- dev_helpers.hpp helper_perf_output
+    if (id == 25) return helper_perf_output(maps, a2, a4, a5, (uint32_t)(env.vcpu % ncpu), win, ml);
     // a QUEUE / STACK map: push / pop / peek, and lookup (a peek that returns
     // the slot), update (a push, the key ignored) and delete (a pop that
     // discards) -- dev_helpers.hpp helper_qs

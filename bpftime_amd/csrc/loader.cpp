@@ -34,6 +34,7 @@ bool device_helper_supported(uint32_t id) {
     case 15: case 16:             // bpf_get_current_uid_gid / _comm (the launching VM's identity)
     case 36:                      // bpf_probe_write_user
     case 125: case 160:           // bpf_ktime_get_boot_ns / _coarse_ns (helper 5's clock)
+    case 25:                      // bpf_perf_event_output (a record in a software perf event's ring)
     case kTailHelper:
       return true;
   }
@@ -266,6 +267,7 @@ static int helper_arity(uint32_t id) {
       return 3;                                // probe_read*(dst, size, src), strncmp(s1, s1_sz, s2)
     case 2: case 189: return 4;                // map_update_elem, xdp_load_bytes
     case kTailHelper: return 3;                // tail_call(ctx, prog_array, index)
+    case 25: return 5;                         // perf_event_output(ctx, map, flags, data, size)
     case (uint32_t)kRetHelper: return 0;       // a linked tail-call target's exit
     default: return 5;                         // csum_diff and anything else
   }
@@ -518,6 +520,8 @@ int load_program(const RawInsn *code, size_t n, const std::map<size_t, size_t> &
       if (mem_helper(cur.imm)) out.bloom = true;  // (helper_mem: the scratch-stack kernels' too)
       if (task_trace_helper(cur.imm)) out.bloom = true;  // (helper_comm / helper_trace: beside helper_mem)
       if (cur.imm == 6) out.trace_printk = true;
+      // (helper_perf_output: beside them; the launch uploads the perf table first)
+      if (cur.imm == 25) out.bloom = out.perf_output = true;
       if (cur.imm == 58 || cur.imm == 187) out.sets_retval = true;
       // bpf_ktime_get_boot_ns / bpf_ktime_get_coarse_ns: a batch has one
       // clock source, so both are helper 5 from here on -- in the analyses,
@@ -1082,6 +1086,7 @@ static void accesses(const std::vector<DInsn> &p, uint32_t i, const std::vector<
     case 89: arg(2); map_values(); return;  // peek: reads the value (Bloom filter) or writes it (QUEUE / STACK)
     case 28: arg(1); arg(3); return;
     case 130: arg(2); return;
+    case 25: arg(4); return;  // perf_event_output reads r4's range (the ring is no map's value)
     case 132: case 133: arg(1); return;
     case 189: arg(3); return;
     // probe_read* / probe_read*_str write r1's range and read r3's; strncmp
@@ -1176,6 +1181,7 @@ static void const_loads(const std::vector<DInsn> &p, const std::vector<uint8_t> 
           case 1: case 5: case 7: case 8: case 14: case 28: case 58: case 187: case 130:
           case 131: case 132: case 133: case 44: case 65:
           case 6: case 15: case 125: case 160:  // (trace_printk reads only, into the log)
+          case 25:                              // (perf_event_output reads only, into a ring)
             break;  // no array-map writes (ring memory, the unit's ctx, dispatch state)
           case 88: case 89:  // pop / peek of a QUEUE / STACK write *value
             writes.push_back(loc_of(p, st[2], 0, kUnknownLen));
@@ -1446,6 +1452,7 @@ static void tail_save_masks(const std::vector<DInsn> &p, const std::vector<std::
         break;
       case 182: break;  // strncmp: reads only
       case 6: case 15: case 125: case 160: break;  // trace_printk reads only; no arguments
+      case 25: break;  // perf_event_output reads only
       default:
         if (d.hi != kRetHelper) {
           cm = 0x3f;
@@ -1553,6 +1560,16 @@ static void map_effects(const std::vector<DInsn> &prog, const std::vector<std::v
             const int32_t t1 = target(i, st[1], 0, 1), t2 = target(i, st[2], 0, 1);
             if (t1 != -2) mark(t1, FX_WRITE);
             if (t2 != -2) mark(t2, FX_READ);
+            break;
+          }
+          case 25: {
+            // perf_event_output(ctx, map, flags, data, size): the map handle
+            // is r2 -- a write of the perf array it names (the records'
+            // order is an effect: two emitting programs do not commute), of
+            // every map when the kinds cannot place r2; reads through r4
+            mark(st[2].kind == P_MAPFD ? st[2].id : -1, FX_WRITE);
+            const int32_t t4 = target(i, st[4], 0, 1);
+            if (t4 != -2) mark(t4, FX_READ);
             break;
           }
           case 6: {  // trace_printk reads the format and what its %s arguments point to

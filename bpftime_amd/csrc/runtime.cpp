@@ -31,11 +31,13 @@ int Runtime::ensure_device() {
     return -1;
   }
   if (hipMemset(arena, 0, arena_size) != hipSuccess) return -1;
-  if (hipMalloc((void **)&d_maptab, sizeof(DMap) * kMaxFds) != hipSuccess) {
+  // (the map table, then the perf table: common.hpp DPerf)
+  if (hipMalloc((void **)&d_maptab, (sizeof(DMap) + sizeof(DPerf)) * kMaxFds) != hipSuccess) {
     set_error("hipMalloc(map table) failed");
     return -1;
   }
-  if (hipMemset(d_maptab, 0, sizeof(DMap) * kMaxFds) != hipSuccess) return -1;
+  if (hipMemset(d_maptab, 0, (sizeof(DMap) + sizeof(DPerf)) * kMaxFds) != hipSuccess) return -1;
+  perf_dirty = true;  // (perf records may be older than the device)
   arena_used = 0;
   return 0;
 }
@@ -49,6 +51,25 @@ uint64_t Runtime::arena_alloc(uint64_t bytes) {
 
 int Runtime::push_map(int fd) {
   return hipMemcpy(d_maptab + fd, &maps[fd].d, sizeof(DMap), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
+}
+
+// The whole perf table from the records: 32 KiB, only when a record changed
+// since the last upload.  Launches that may still run read only the entries
+// of rings they write, which a ring's lifetime keeps unchanged.
+int Runtime::push_perfs() {
+  if (!perf_dirty) return 0;
+  if (ensure_device() < 0) return -1;
+  std::vector<DPerf> t(kMaxFds, DPerf{});
+  for (uint32_t fd = 0; fd < kMaxFds; fd++) {
+    if (kind[fd] != HKind::PERF || perfs[fd].type != 1) continue;
+    t[fd].soft = 1;
+    t[fd].ring = perfs[fd].ring;
+    t[fd].data_bytes = perfs[fd].ring_bytes;
+  }
+  if (hipMemcpy((void *)(d_maptab + kMaxFds), t.data(), sizeof(DPerf) * kMaxFds, hipMemcpyHostToDevice) != hipSuccess)
+    return -1;
+  perf_dirty = false;
+  return 0;
 }
 
 int alloc_fd(int fd) {
@@ -105,7 +126,9 @@ void bpftime_close(int fd) {
       detach = r.links[fd].attach_id;
       r.links[fd] = LinkRec();
     } else if (r.kind[fd] == HKind::PERF) {
+      // (its ring goes with the record; the arena's bytes come back at reset)
       r.perfs[fd] = PerfRec();
+      r.perf_dirty = true;
     }
     r.kind[fd] = HKind::NONE;
   }
@@ -133,7 +156,8 @@ void bpftime_amd_reset(void) {
   r.lpm_maps = 0;
   (void)detach;
   syscall_detach_all();  // the link-made attachments and the direct ones
-  if (r.d_maptab) hipMemset(r.d_maptab, 0, sizeof(DMap) * kMaxFds);
+  if (r.d_maptab) hipMemset(r.d_maptab, 0, (sizeof(DMap) + sizeof(DPerf)) * kMaxFds);
+  r.perf_dirty = false;  // (no perf record is left, and the table says so)
   r.arena_used = 0;
   r.trace_printk_on = false;
   r.prog_gen++;  // tail-call images linked before the reset relink

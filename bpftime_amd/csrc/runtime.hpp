@@ -39,6 +39,7 @@ struct MapRec {
   // ARRAY_OF_MAPS: the host's copy of the slots (map_arrmaps.cpp keeps it equal
   // to the arena's).  The launch walk (vm_api.cpp inner_launch_check) reads the
   // inner fds here, never from device memory
+  // (PERF_EVENT_ARRAY: the same mirror of its perf event fds, map_perfarr.cpp)
   std::vector<int32_t> inner_slots;
   // BPF_MAP_CREATE attributes as given (BPF_OBJ_GET_INFO_BY_FD reports them)
   uint32_t ifindex = 0, btf_vmlinux_value_type_id = 0, btf_id = 0, btf_key_type_id = 0, btf_value_type_id = 0;
@@ -68,6 +69,9 @@ struct PerfRec {
   int cpu = 0;                 // software perf event
   int32_t sample_type = 0;
   int64_t config = 0;
+  // software perf event: its device ring (common.hpp DPerf), 0 until
+  // bpftime_amd_perf_event_mmap gives it one (handles.cpp)
+  uint64_t ring = 0, ring_bytes = 0;
 };
 
 struct ProgRec {
@@ -112,6 +116,12 @@ struct Runtime {
   int ensure_device();          // lazily picks the current device, allocates arena + table
   uint64_t arena_alloc(uint64_t bytes);
   int push_map(int fd);         // upload DMap entry for fd
+  // The device's perf table (common.hpp DPerf) lives behind the map table.
+  // perf_dirty: a perf record was made, given a ring, closed or reset since
+  // the table was uploaded; a launch of a program that calls
+  // bpf_perf_event_output uploads it first (push_perfs; the caller holds mu)
+  bool perf_dirty = false;
+  int push_perfs();
   std::set<int> ix_stale;       // hash maps whose lookup index needs a rebuild
   std::set<int> lpm_stale;      // LPM tries whose device replica needs an upload
   std::set<int> lpm_flat_pending;  // IPv4 LPM tries whose flat table is not built (DMap.ix = 0: walk)

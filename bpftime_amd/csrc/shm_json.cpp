@@ -308,6 +308,18 @@ int import_handler(int fd, const J &v, std::string &err, std::vector<std::pair<i
       err = "map " + std::to_string(fd) + ": " + bpftime_amd_last_error();
       return -1;
     }
+    // a PERF_EVENT_ARRAY's slots (this runtime's export, see above)
+    if (const J *sl = v.get("slots"); sl && sl->k == J::ARR && a.type == (int)MT_PERF_EVENT_ARRAY) {
+      for (size_t i = 0; i < sl->a.size(); i++) {
+        bool k = true;
+        const int32_t val = (int32_t)num(&sl->a[i], &k);
+        const uint32_t key = (uint32_t)i;
+        if (!k || (val != -1 && bpftime_map_update_elem(fd, &key, &val, 0) < 0)) {
+          err = "map " + std::to_string(fd) + ": bad slot " + std::to_string(i);
+          return -1;
+        }
+      }
+    }
     return 0;
   }
   if (type->s == "bpf_prog_handler") {
@@ -537,7 +549,15 @@ int bpftime_export_global_shm_to_json(const char *filename) {
                  m.btf_id, m.btf_key_type_id, m.btf_value_type_id, m.btf_vmlinux_value_type_id,
                  (unsigned long long)m.flags, m.ifindex, m.kernel_bpf_map_id, m.key_size,
                  (unsigned long long)m.map_extra, m.type, m.max_entries, m.value_size);
-        item = std::string(buf) + "\"name\": " + quote(m.name) + ", \"type\": \"bpf_map_handler\"}";
+        // (a PERF_EVENT_ARRAY's perf event fds, from the host mirror: this
+        // runtime's addition, the reference's export has no map contents)
+        std::string slots;
+        if (m.type == MT_PERF_EVENT_ARRAY) {
+          slots = ", \"slots\": [";
+          for (size_t i = 0; i < m.inner_slots.size(); i++) slots += (i ? ", " : "") + std::to_string(m.inner_slots[i]);
+          slots += "]";
+        }
+        item = std::string(buf) + "\"name\": " + quote(m.name) + slots + ", \"type\": \"bpf_map_handler\"}";
       } else if (r.kind[fd] == HKind::PROG) {
         const ProgRec &p = r.progs[fd];
         item = "{\"attr\": {\"cnt\": " + std::to_string(p.insns.size() / 8) + ", \"insns\": \"" +

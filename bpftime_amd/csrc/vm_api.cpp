@@ -191,6 +191,23 @@ static bool inner_launch_check(const FastForm &f, std::string &error) {
   return true;
 }
 
+// bpf_perf_event_output: the device's perf table (common.hpp DPerf) as the
+// records stand now -- which fds are software perf events, and their rings --
+// before a launch of a program that calls the helper is queued.  Under the
+// runtime lock; nothing is uploaded when no record changed since the last
+// upload.  The slots of the perf arrays are the device's own copy, which a
+// host write changes only after the device has finished (map_perfarr.cpp).
+static bool perf_launch_prepare(const LoadOut &prog, std::string &error) {
+  if (!prog.perf_output) return true;
+  Runtime &r = rt();
+  std::lock_guard<std::mutex> g(r.mu);
+  if (r.push_perfs() < 0) {
+    error = "perf table upload failed";
+    return false;
+  }
+  return true;
+}
+
 extern "C" int bpftime_amd_occupancy(uint32_t kind, bool big_stack, size_t dyn_lds, bool gregs, uint32_t block,
                                     bool image);
 extern "C" size_t bpftime_amd_static_lds_image(uint32_t kind, bool big_stack, bool gregs, uint32_t block, bool image);
@@ -780,6 +797,7 @@ int Mi355xVm::exec_batch(const ebpf_batch *b) {
   Image &im = *imp;
   // ARRAY_OF_MAPS: the inner maps the slots name, before anything is queued
   if (!inner_launch_check(kind == CTX_XDP ? im.fx : im.fr, error)) return -1;
+  if (!perf_launch_prepare(im.prog, error)) return -1;
   // the unwind helper as the device knows helpers (bpftime ids): the
   // registration that was given ubpf id unwind_idx
   int32_t unwind_helper = -1;
@@ -1510,6 +1528,7 @@ int64_t seq_dispatch(const std::vector<SeqAttach> &progs, const SysLayout &lay, 
     {  // ARRAY_OF_MAPS: the inner maps its slots name (as exec_batch)
       std::string ie;
       if (!inner_launch_check(im->fr, ie)) return fail(ie);
+      if (!perf_launch_prepare(im->prog, ie)) return fail(ie);
     }
     {  // QUEUE / STACK maps: lanes in thread order are not record order across threads
       std::string qe;
@@ -1717,7 +1736,7 @@ int bpftime_amd_register_default_helpers(struct ebpf_vm *vm) {
            {115, "bpf_probe_read_kernel_str"}, {182, "bpf_strncmp"},
            {15, "bpf_get_current_uid_gid"},  {16, "bpf_get_current_comm"},
            {36, "bpf_probe_write_user"},     {125, "bpf_ktime_get_boot_ns"},
-           {160, "bpf_ktime_get_coarse_ns"}};
+           {160, "bpf_ktime_get_coarse_ns"}, {25, "bpf_perf_event_output"}};
   int err = 0;
   for (auto &e : h) err |= ebpf_register(vm, e.id, e.name, nullptr);
   // ... and bpf_trace_printk once the host enabled it (bpftime_amd_enable_trace_printk)

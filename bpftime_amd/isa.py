@@ -85,11 +85,13 @@ BPF_FUNC_get_current_comm = 16
 BPF_FUNC_probe_write_user = 36
 BPF_FUNC_ktime_get_boot_ns = 125
 BPF_FUNC_ktime_get_coarse_ns = 160
+BPF_FUNC_perf_event_output = 25
 
 # map types (linux/bpf.h)
 BPF_MAP_TYPE_HASH = 1
 BPF_MAP_TYPE_ARRAY = 2
 BPF_MAP_TYPE_PROG_ARRAY = 3
+BPF_MAP_TYPE_PERF_EVENT_ARRAY = 4
 BPF_MAP_TYPE_PERCPU_HASH = 5
 BPF_MAP_TYPE_PERCPU_ARRAY = 6
 BPF_MAP_TYPE_LRU_HASH = 9

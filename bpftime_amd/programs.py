@@ -20,7 +20,7 @@ import struct
 
 from .isa import (Asm, BPF_ANY, BPF_FUNC_get_current_pid_tgid, BPF_FUNC_ktime_get_ns, BPF_FUNC_map_lookup_elem,
                   BPF_FUNC_map_update_elem, BPF_FUNC_override_return, BPF_FUNC_set_retval,
-                  BPF_FUNC_ringbuf_output, BPF_NOEXIST, ATOMIC_ADD, XDP_DROP, XDP_PASS, XDP_TX, XDP_ABORTED)
+                  BPF_FUNC_ringbuf_output, BPF_FUNC_perf_event_output, BPF_NOEXIST, ATOMIC_ADD, XDP_DROP, XDP_PASS, XDP_TX, XDP_ABORTED)
 
 ETH_P_IP_LE = 0x0008  # htons(0x0800) as read by a little-endian ldxh
 IPPROTO_TCP, IPPROTO_UDP = 6, 17
@@ -901,3 +901,23 @@ def tenant_counter_bound(inner_fd: int) -> bytes:
     a.mov64(0, XDP_PASS)
     a.label("out").exit()
     return a.assemble()
+
+
+# ---- BPF_MAP_TYPE_PERF_EVENT_ARRAY (bpf_perf_event_output) -------------------
+def perf_event_emitter(map_fd: int, size: int = 32, flags: int = 0xFFFFFFFF) -> bytes:
+    """One event per unit: the unit's first `size` bytes go to the perf event in
+    the slot of the unit's CPU (flags BPF_F_CURRENT_CPU, which the reference
+    does not read).  r0 = the helper's answer (0, also for a dropped event).
+    map_fd: PERF_EVENT_ARRAY with a slot per CPU."""
+    a = Asm()
+    a.mov64(4, "r1").ld_map_fd(2, map_fd).lddw(3, flags).mov64(5, size)
+    a.call(BPF_FUNC_perf_event_output)
+    return a.exit().assemble()
+
+
+def ringbuf_emitter(rb_fd: int, size: int = 32) -> bytes:
+    """perf_event_emitter's event through bpf_ringbuf_output instead."""
+    a = Asm()
+    a.mov64(2, "r1").ld_map_fd(1, rb_fd).mov64(3, size).mov64(4, 0)
+    a.call(BPF_FUNC_ringbuf_output)
+    return a.exit().assemble()

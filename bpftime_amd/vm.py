@@ -15,6 +15,7 @@ import numpy as np
 
 from . import isa
 from ._lib import BpfLinkCreateArgs, BpfMapAttr, EbpfBatch, LaunchInfo, SysRecords, TraceLine, lib
+from ._lib import PerfEvent as PerfEventRec
 
 CTX_RAW, CTX_XDP, CTX_SYSCALL, CTX_SYSCALL_EXIT = 0, 1, 2, 3
 SYSCALL_RECORD, SYSCALL_RECORD_FULL, SYSCALL_RECORD_TIMED = 64, 96, 128  # include/bpftime_amd.h replay records
@@ -74,6 +75,60 @@ class DeviceBuffer:
             self.free()
         except Exception:
             pass
+
+
+# ---------------------------------------------------------------------------
+# software perf events: the consumer side of bpf_perf_event_output
+# ---------------------------------------------------------------------------
+class PerfEvent:
+    """A software perf event record (PERF_TYPE_SOFTWARE) and its device ring:
+    what a PERF_EVENT_ARRAY slot names.  mmap() gives it the ring, as the
+    consumer's mmap of the perf fd does in the reference."""
+
+    def __init__(self, cpu: int = 0, fd: int = -1, type_: int = 1, sample_type: int = 1 << 10, config: int = 10,
+                 data_bytes: int = 0):
+        e = PerfEventRec(type=type_, pid=-1, enabled=0, tracepoint_id=-1, sys_nr=-1, cpu=cpu,
+                         sample_type=sample_type, config=config)
+        self.fd = lib().bpftime_amd_perf_event_record(fd, C.byref(e))
+        if self.fd < 0:
+            raise EbpfError(f"perf event create failed: {_err()}")
+        if data_bytes:
+            self.mmap(data_bytes)
+
+    def mmap(self, data_bytes: int) -> None:
+        if lib().bpftime_amd_perf_event_mmap(self.fd, data_bytes) < 0:
+            raise EbpfError(f"perf event mmap failed: {_err()}")
+
+    def state(self):
+        """(data_head, data_tail, data_bytes); data_bytes 0: no ring yet."""
+        h, t, b = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        if lib().bpftime_amd_perf_event_ring_state(self.fd, C.byref(h), C.byref(t), C.byref(b)) < 0:
+            raise EbpfError(f"fd {self.fd} is not a software perf event")
+        return h.value, t.value, b.value
+
+    def fetch_raw(self, cap: int = 1 << 20):
+        """(record count, the records' bytes back to back as they lie in the
+        ring): bpftime_amd_perf_event_fetch."""
+        buf = C.create_string_buffer(max(cap, 1))
+        used = C.c_uint64(0)
+        n = lib().bpftime_amd_perf_event_fetch(self.fd, buf, cap, C.byref(used))
+        if n < 0:
+            raise EbpfError(f"perf event fetch failed: {_err()}")
+        return n, buf.raw[:used.value]
+
+    def fetch(self, cap: int = 1 << 20) -> list:
+        """The samples' data: per record the `size` bytes behind the 12-byte
+        header (the data, then the padding to 8)."""
+        n, raw = self.fetch_raw(cap)
+        out, off = [], 0
+        for _ in range(n):
+            rs = int.from_bytes(raw[off + 6:off + 8], "little")
+            out.append(raw[off + 12:off + rs])
+            off += rs
+        return out
+
+    def close(self) -> None:
+        lib().bpftime_close(self.fd)
 
 
 # ---------------------------------------------------------------------------
@@ -191,6 +246,17 @@ class Map:
 
     def inner_fds(self) -> list:
         """ARRAY_OF_MAPS: the int each slot holds (0: empty), from a snapshot."""
+        return [int(x) for x in self.snapshot().view(np.int32)]
+
+    # BPF_MAP_TYPE_PERF_EVENT_ARRAY (perf_event_array_map.cpp)
+    def set_perf(self, index: int, perf, flags: int = 0) -> int:
+        """PERF_EVENT_ARRAY: store the perf event `perf` (a PerfEvent or a raw
+        int: the slots are untyped) in slot `index`."""
+        fd = perf.fd if isinstance(perf, PerfEvent) else int(perf)
+        return self.update(struct.pack("<i", index), struct.pack("<i", fd), flags)
+
+    def perf_fds(self) -> list:
+        """PERF_EVENT_ARRAY: the int each slot holds (-1: empty), from a snapshot."""
         return [int(x) for x in self.snapshot().view(np.int32)]
 
     # BPF_MAP_TYPE_QUEUE / _STACK / _BLOOM_FILTER (bpftime_shm.cpp:168-200)

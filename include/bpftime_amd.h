@@ -55,7 +55,15 @@ struct bpf_link_create_args {
 /* create a map at `fd` (-1: lowest unused fd).  Supported types: HASH (1,
  * fix-size hash, map_handler.cpp:54-58), ARRAY (2), PROG_ARRAY (3, prog
  * fds, prog_array.cpp; the targets of bpf_tail_call, linked into the caller's
- * image at launch), PERCPU_HASH (5), PERCPU_ARRAY (6), LRU_HASH (9),
+ * image at launch), PERF_EVENT_ARRAY (4, perf_event_array_map.cpp: key_size
+ * and value_size must be 4, else -1 + EINVAL; max_entries int32 slots, all
+ * -1 at first, each the fd of a software perf event.  Lookup returns the
+ * slot, update stores the int with the flags ignored, delete stores -1, each
+ * -1 / NULL + EINVAL for a key < 0 or >= max_entries; get_next_key: 0 for a
+ * NULL key, -1 + ENOENT for the last key, -1 + EINVAL out of range, else key
+ * + 1.  A program's bpf_perf_event_output(ctx, map, flags, data, size) writes
+ * a sample to the ring of the perf event in the slot of its CPU, see
+ * bpftime_amd_perf_event_mmap), PERCPU_HASH (5), PERCPU_ARRAY (6), LRU_HASH (9),
  * LPM_TRIE (11), ARRAY_OF_MAPS (12, map_in_maps.hpp: max_entries int32 slots
  * whatever value_size says, each the fd of an inner map or 0; there is no
  * inner_map_fd, so a slot takes any int.  The host writes slots with
@@ -173,6 +181,35 @@ struct bpftime_amd_perf_event {
 };
 int bpftime_amd_perf_event_record(int fd, const struct bpftime_amd_perf_event *e);
 int bpftime_amd_perf_event_get(int fd, struct bpftime_amd_perf_event *e);
+/* The ring of a software perf event (type 1; software_perf_event_buffer,
+ * perf_event_handler.cpp:235-450): what a program's bpf_perf_event_output
+ * (helper 25) writes to through a PERF_EVENT_ARRAY slot that holds the fd.
+ * The reference sizes the buffer when the consumer mmaps the perf fd; until
+ * then every output is dropped.
+ *
+ * _mmap gives the perf event a device ring of data_bytes (a power of two, at
+ * least 64): u64 data_head and u64 data_tail on a 128-byte line each, then
+ * the data bytes, in the map arena.  A second call with the same size does
+ * nothing; another size is -1 + EINVAL: a ring cannot be resized.  -1 +
+ * EINVAL too for an fd that is no software perf event or a size that is no
+ * power of two; -1 + ENOMEM when the arena is exhausted.  Closing the fd and
+ * bpftime_amd_reset drop the ring.
+ *
+ * _fetch is the consumer: it waits for the device, walks the records from
+ * data_tail to data_head and copies each whole record -- the 8-byte
+ * perf_event_header {u32 type = 9 PERF_RECORD_SAMPLE, u16 misc = 0, u16
+ * size}, the u32 data size (size - 12), the data and the padding to 8 -- to
+ * `out`, unwrapped and back to back, stopping at the first that does not fit
+ * in cap; writes the new data_tail back; returns the record count and sets
+ * *used to the bytes written.  A record whose header size is < 8 or larger
+ * than the ring drops everything left (copy_next_record_to, :409-450).  0 for
+ * a perf event without a ring; -1 for an fd that is no software perf event.
+ *
+ * _ring_state reads the positions (it waits for the device too) and the
+ * ring's size; all 0 before _mmap.  Any out pointer may be NULL. */
+int bpftime_amd_perf_event_mmap(int perf_fd, uint64_t data_bytes);
+int64_t bpftime_amd_perf_event_fetch(int perf_fd, void *out, uint64_t cap, uint64_t *used);
+int bpftime_amd_perf_event_ring_state(int perf_fd, uint64_t *head, uint64_t *tail, uint64_t *data_bytes);
 /* bpftime_shm.cpp:249-253 (BPF_PROG_ATTACH): link prog bpf_fd to the perf
  * event: a link fd whose close detaches it; a program linked to a sys_enter
  * tracepoint then runs in bpftime_amd_syscall_dispatch.  -1 + ENOENT when
@@ -225,7 +262,9 @@ int bpftime_amd_map_geometry(int fd, uint64_t *nbuckets, uint32_t *slot_size, ui
 /* (a QUEUE / STACK map: tail - head) */
 uint64_t bpftime_amd_map_count(int fd);
 /* 1 when this build has a map family for the BPF_MAP_TYPE_* number, else 0
- * (needs no device) */
+ * (needs no device).  PERF_EVENT_ARRAY (4) is the exception: the family
+ * exists and bpftime_maps_create makes one, but this query keeps answering 0
+ * for it, as it did before the family was added. */
 int bpftime_amd_map_type_supported(uint32_t type);
 /* BLOOM_FILTER: the jhash seed (drawn at random per map, as the reference
  * draws it) to *out; a non-NULL `set` installs *set first and zeroes the bit

@@ -54,8 +54,8 @@ void ebpf_set_error_print(struct ebpf_vm *vm, int (*error_printf)(FILE *stream, 
  * implementation of ids 1,2,3 (map lookup / update / delete), 5 (ktime_get_ns),
  * 4 / 112 / 113 (probe_read / _user / _kernel), 6 (trace_printk, once bpftime_amd_enable_trace_printk(1)), 7
  * (get_prandom_u32), 8 (get_smp_processor_id), 12 (tail_call), 14
- * (get_current_pid_tgid), 15 (get_current_uid_gid), 16 (get_current_comm), 28
- * (csum_diff), 36 (probe_write_user), 44 (xdp_adjust_head), 45 / 114 / 115
+ * (get_current_pid_tgid), 15 (get_current_uid_gid), 16 (get_current_comm), 25
+ * (perf_event_output), 28 (csum_diff), 36 (probe_write_user), 44 (xdp_adjust_head), 45 / 114 / 115
  * (probe_read_str / _user_str / _kernel_str), 58 (override_return), 65
  * (xdp_adjust_tail), 87-89 (map push / pop / peek), 125 / 160
  * (ktime_get_boot_ns / _coarse_ns), 130-133 (ringbuf output / reserve / submit /
