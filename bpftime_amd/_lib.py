@@ -39,7 +39,10 @@ class EbpfBatch(C.Structure):  # include/ebpf-vm.h struct ebpf_batch
                 ("umem_bytes", C.c_uint64), ("sys_nr", C.c_int64), ("sys_state", C.c_void_p),
                 ("sys_ret", C.c_void_p), ("sys_phase", C.c_uint32), ("pid_tgid_off", C.c_int32),
                 ("ktime_off", C.c_int32), ("pid_tgid_arr", C.c_void_p), ("pid_tgid_stride", C.c_uint64),
-                ("ktime_arr", C.c_void_p), ("ktime_stride", C.c_uint64)]
+                ("ktime_arr", C.c_void_p), ("ktime_stride", C.c_uint64),
+                ("stack_arr", C.c_void_p), ("stack_unit_stride", C.c_uint64),
+                ("stack_frame_stride", C.c_uint64), ("stack_depths", C.c_void_p),
+                ("stack_fixed_depth", C.c_uint32), ("stack_max_depth", C.c_uint32)]
 
 
 class SysRecords(C.Structure):  # include/bpftime_amd.h struct bpftime_amd_sys_records
@@ -97,6 +100,7 @@ SIGNATURES = [
     ("bpftime_map_peek_elem", C.c_long, [C.c_int, C.c_void_p]),
     ("bpftime_amd_map_type_supported", C.c_int, [C.c_uint32]),
     ("bpftime_amd_bloom_seed", C.c_int, [C.c_int, u32p, u32p]),
+    ("bpftime_amd_stack_trace_get", C.c_int, [C.c_int, C.c_uint32, u64p, C.c_uint32]),
     ("bpftime_map_value_size_from_syscall", C.c_uint32, [C.c_int]),
     ("bpftime_is_map_fd", C.c_int, [C.c_int]),
     ("bpftime_is_array_map", C.c_int, [C.c_int]),

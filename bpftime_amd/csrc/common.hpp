@@ -84,6 +84,7 @@ constexpr uint32_t MT_PROG_ARRAY = 3;
 constexpr uint32_t MT_PERF_EVENT_ARRAY = 4;
 constexpr uint32_t MT_PERCPU_HASH = 5;
 constexpr uint32_t MT_PERCPU_ARRAY = 6;
+constexpr uint32_t MT_STACK_TRACE = 7;
 constexpr uint32_t MT_LRU_HASH = 9;
 constexpr uint32_t MT_LPM_TRIE = 11;
 constexpr uint32_t MT_ARRAY_OF_MAPS = 12;
@@ -135,6 +136,9 @@ constexpr uint32_t MT_BLOOM_FILTER = 30;
 //                  empty (perf_event_array_map.cpp:14-26); written by the host
 //                  only.  bpf_perf_event_output reads the slot of the lane's
 //                  CPU and finds the fd's ring in the perf table (DPerf below)
+//   STACK_TRACE    max_entries slots of slot_size = 16 + value_size bytes at
+//                  data: {u64 claim (all ones: none), u32 nframes, u32 full,
+//                  u64 frames[value_size / 8]} (st_* below)
 struct DMap {
   uint32_t type;
   uint32_t key_size;
@@ -172,6 +176,51 @@ constexpr uint32_t kPerfRingHdr = 256;     // head line + tail line
 constexpr uint32_t kPerfTailOff = 128;
 constexpr uint32_t kPerfRecHdr = 12;       // perf_event_header (8) + u32 size: perf_sample_raw
 constexpr uint64_t kPerfMaxData = 65535 - kPerfRecHdr - 7;  // output_data's E2BIG bound (:359-363)
+
+// STACK_TRACE (runtime/src/bpf_map/userspace/stack_trace_map.cpp).  Slot `id`
+// holds the stack whose hash is id modulo max_entries: `full` 0 = no entry,
+// else nframes frames and zeros to value_size.  `claim` is all ones outside a
+// parallel batch; inside one, bpf_get_stackid lowers it to the serial-order key
+// of the call that would have filled the empty slot first (st_claim_key), and
+// k_stack_commit (stack_commit.hip) stores that call's frames afterwards.
+constexpr uint32_t kStHdr = 16;           // claim, nframes, full
+constexpr uint32_t kStMaxDepth = 127;     // frames a recorded stack may have (ebpf_batch::stack_max_depth)
+constexpr uint64_t kStNoClaim = ~0ull;
+constexpr uint64_t kStUserStack = 1ull << 8, kStFastCmp = 1ull << 9, kStReuse = 1ull << 10, kStBuildId = 1ull << 11;
+inline BA_HD uint64_t st_slot(const DMap &m, uint64_t id) { return m.data + id * m.slot_size; }
+// (unit << 16 | min(call_seq, 255) << 8 | skip: exact up to 255 calls per unit)
+inline BA_HD uint64_t st_claim_key(uint64_t global_unit, uint32_t call_seq, uint32_t skip) {
+  return global_unit << 16 | (uint64_t)(call_seq < 255 ? call_seq : 255) << 8 | (skip & 0xff);
+}
+// boost::hash_combine on a 64-bit size_t (Boost 1.74 container_hash/hash.hpp,
+// hash_combine_impl(uint64_t &, uint64_t)), as stack_trace_map.hpp:27-35 uses it
+inline BA_HD uint64_t st_hash_combine(uint64_t h, uint64_t k) {
+  const uint64_t m = 0xc6a4a7935bd1e995ull;
+  k *= m;
+  k ^= k >> 47;
+  k *= m;
+  h ^= k;
+  h *= m;
+  return h + 0xe6546b64ull;
+}
+
+// The recorded call stacks of a batch (include/ebpf-vm.h ebpf_batch::stack_*):
+// frame k of unit i at arr + i * unit_stride + k * frame_stride; arr null: no
+// stack source.  A unit's depth is depths[i] (null: fixed_depth), clamped to
+// max_depth wherever it is read.
+struct StackSrc {
+  const uint8_t *arr;
+  uint64_t unit_stride, frame_stride;
+  const uint32_t *depths;
+  uint32_t fixed_depth, max_depth;
+};
+inline BA_HD uint32_t st_depth(const StackSrc &s, uint64_t unit) {
+  const uint32_t d = s.depths ? s.depths[unit] : s.fixed_depth;
+  return d < s.max_depth ? d : s.max_depth;
+}
+inline BA_HD uint64_t st_frame(const StackSrc &s, uint64_t unit, uint32_t k) {
+  return *(const uint64_t *)(s.arr + unit * s.unit_stride + k * s.frame_stride);
+}
 
 // QUEUE / STACK (runtime/src/bpf_map/userspace/queue.cpp, stack.cpp).  Push
 // writes the slot of ticket `tail`; a queue pops at `head`, a stack at `tail -
@@ -445,6 +494,9 @@ struct KParams {
   uint64_t task_comm[8];
   uint8_t *trace_log;
   uint64_t trace_cap;
+  // the units' recorded call stacks (bpf_get_stackid / bpf_get_stack), indexed
+  // by the unit's index in the batch; read like the identity above
+  StackSrc stacks;
 };
 
 // Where a syscall replay's fields live (include/bpftime_amd.h): record i's

@@ -1505,6 +1505,15 @@ struct TaskEnv {
   uint8_t *trace_log;  // the trace log (trace_fmt.hpp), or null
   uint64_t trace_cap;  // its records
   uint64_t unit;       // the calling unit's global index
+  // the batch's recorded call stacks (common.hpp StackSrc; arr null: no stack
+  // source) and the calling unit's index in the batch, which indexes them
+  StackSrc stacks;
+  uint64_t stack_unit;
+  // bpf_get_stackid calls the unit has made so far (common.hpp st_claim_key).
+  // Here and not in LaneEnv, which every instance of the kernels passes to
+  // out-of-line helpers by address: a field more there grew the scratch frame
+  // of two LDS-stack instances of k_interp
+  uint32_t st_calls;
 };
 
 // bpf_get_current_comm(buf, size) = strncpy(buf, comm, size): comm up to and
@@ -1758,6 +1767,99 @@ __device__ __noinline__ uint64_t helper_perf_output(const DMap *maps, uint64_t m
     if (size > first) mem_copy(base, data + first, size - first);
   }
   return ret;
+}
+
+// ---------------------------------------------------------------------------
+// bpf_get_stackid(ctx, map, flags) (27) and bpf_get_stack(ctx, buf, size,
+// flags) (67): bpf_helper.cpp:791-893 over stack_trace_map.cpp:96-137.  The
+// stack is the unit's recorded one (TaskEnv::stacks), where the reference asks
+// the uprobe attach implementation for the caller's.  Checks, in its order:
+//   BPF_F_USER_STACK clear: -ENOTSUP;  (67) BPF_F_USER_BUILD_ID set: -ENOTSUP;
+//   no stack source (the attach implementation not registered): -ENOTSUP;
+//   a unit with no frames (generate_stack returned nullptr): -ENOENT;
+//   the first `flags & 0xff` frames are dropped; a stack that loses all of
+//   them is empty, and is still hashed and stored.
+// 27 then needs a STACK_TRACE map in r2: anything else answers -EINVAL (the
+// reference dereferences the empty optional try_get_stack_trace_impl returns).
+// id = hash % max_entries is the answer whatever happens to the slot.
+// Every loop is per lane and bounded by kStMaxDepth; no lane waits on another.
+// ---------------------------------------------------------------------------
+constexpr uint64_t kStEnotsup = (uint64_t)(int64_t)-95, kStEnoent = (uint64_t)(int64_t)-2,
+                   kStEinval = (uint64_t)(int64_t)-22;
+
+// An ORDERED batch's lane applies fill_stack_trace on the spot: an empty slot
+// takes the stack; an occupied one keeps its own unless the lengths differ,
+// FAST_STACK_CMP is clear and REUSE_STACKID is set (the reference's "equal" is
+// the lengths' equality).  A parallel batch: a slot that was full before the
+// batch stays; for any other the call lowers the slot's claim word to its
+// serial-order key with one relaxed agent-scope atomic min, and k_stack_commit
+// stores the winner's frames after the batch (the launch refuses REUSE_STACKID).
+__device__ __noinline__ uint64_t helper_stackid(const DMap *maps, uint64_t map, uint64_t flags, TaskEnv &te,
+                                                bool exact) {
+  const uint32_t seq = te.st_calls++;
+  if (!(flags & kStUserStack) || !te.stacks.arr) return kStEnotsup;
+  const uint32_t depth = st_depth(te.stacks, te.stack_unit);
+  if (depth == 0) return kStEnoent;
+  const uint32_t skip = (uint32_t)(flags & 0xff);
+  const uint32_t n = depth > skip ? depth - skip : 0;
+  uint64_t h = st_hash_combine(0, n);
+  for (uint32_t k = 0; k < n; k++) h = st_hash_combine(h, st_frame(te.stacks, te.stack_unit, skip + k));
+  if (map >= kMaxFds) return kStEinval;
+  const DMap m = maps[map];
+  if (m.type != MT_STACK_TRACE) return kStEinval;
+  const uint64_t id = h % m.max_entries;
+  const uint64_t slot = st_slot(m, id);
+  if (!exact) {
+    if (*(const volatile uint32_t *)(slot + 12) == 0)
+      __hip_atomic_fetch_min((uint64_t *)slot, st_claim_key(te.unit, seq, skip), __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+    return (uint32_t)id;
+  }
+  const uint32_t have = *(const volatile uint32_t *)(slot + 8), full = *(const volatile uint32_t *)(slot + 12);
+  if (full && ((flags & kStFastCmp) || have == n || !(flags & kStReuse))) return (uint32_t)id;
+  // (n <= stack_max_depth <= value_size / 8: the launch check)
+  const uint32_t cap = m.value_size / 8, nn = n < cap ? n : cap;
+  for (uint32_t k = 0; k < cap; k++)
+    *(volatile uint64_t *)(slot + kStHdr + 8ull * k) = k < nn ? st_frame(te.stacks, te.stack_unit, skip + k) : 0;
+  *(volatile uint64_t *)(slot + 8) = (uint64_t)nn | 1ull << 32;
+  return (uint32_t)id;
+}
+
+// 67: the reference copies min(frames after the skip, size) BYTES of the
+// frames (it compares a frame count with a byte count) and answers 0.  The
+// bytes written are a range the guard accepted first, else -EFAULT and nothing
+// is written; no bytes to write (size 0, or every frame skipped): 0.
+__device__ __noinline__ uint64_t helper_getstack(uint64_t buf, uint64_t size, uint64_t flags, const TaskEnv &te, Win win,
+                                                 MemLane ml) {
+  if (!(flags & kStUserStack) || (flags & kStBuildId) || !te.stacks.arr) return kStEnotsup;
+  const uint32_t depth = st_depth(te.stacks, te.stack_unit);
+  if (depth == 0) return kStEnoent;
+  const uint32_t skip = (uint32_t)(flags & 0xff);
+  const uint64_t n = depth > skip ? depth - skip : 0;
+  const uint64_t bytes = n < size ? n : size;
+  if (bytes == 0) return 0;
+  if (!mem_range_ok(win, ml, buf, bytes)) return kEfault;
+  for (uint32_t i = 0; i < (uint32_t)bytes; i++)
+    mem_st8(buf + i, (uint8_t)(st_frame(te.stacks, te.stack_unit, skip + i / 8) >> (8 * (i % 8))));
+  return 0;
+}
+
+// A program's helpers 1 / 2 / 3 on a STACK_TRACE map (stack_trace_map.cpp:36-94;
+// ORDERED batches only, the launch refuses 1 / 3 elsewhere): lookup yields the
+// slot's frames or NULL, update answers -ENOTSUP, delete empties the slot (0)
+// or answers -1; a NULL key is NULL / -1.
+__device__ __noinline__ uint64_t helper_stmap(const DMap *maps, uint64_t fd, uint64_t key, uint32_t op) {
+  if (op == 2) return kStEnotsup;
+  const uint64_t fail = op == 1 ? 0 : (uint64_t)-1;
+  if (key == 0) return fail;
+  const DMap m = maps[fd];
+  const uint32_t k = *(const u32u *)key;
+  if (k >= m.max_entries) return fail;
+  const uint64_t slot = st_slot(m, k);
+  if (*(const volatile uint32_t *)(slot + 12) == 0) return fail;
+  if (op == 1) return slot + kStHdr;
+  *(volatile uint64_t *)(slot + 8) = 0;
+  return 0;
 }
 
 __device__ uint64_t helper_lookup(const DMap *maps, uint64_t fd, uint64_t key, LaneEnv &env) {

@@ -47,7 +47,7 @@ template <bool BLOOM>
 __device__ __forceinline__ uint64_t call_helper(uint32_t id, uint64_t a1, uint64_t a2, uint64_t a3, uint64_t a4,
                                                 uint64_t a5, const DMap *maps, uint32_t ncpu, uint64_t seed,
                                                 LaneEnv &env, uint32_t *err, const Win &win, const MemLane &ml,
-                                                const TaskEnv &te) {
+                                                TaskEnv &te) {
   if constexpr (BLOOM) {
     // the launching VM's identity and bpf_trace_printk's record log --
     // dev_helpers.hpp helper_comm / helper_trace
@@ -62,6 +62,10 @@ __device__ __forceinline__ uint64_t call_helper(uint32_t id, uint64_t a1, uint64
     // bpf_perf_event_output(ctx, map, flags, data, size): the map is r2, ctx
     // and flags are not read -- dev_helpers.hpp helper_perf_output
     if (id == 25) return helper_perf_output(maps, a2, a4, a5, (uint32_t)(env.vcpu % ncpu), win, ml);
+    // bpf_get_stackid(ctx, map, flags) / bpf_get_stack(ctx, buf, size, flags):
+    // the unit's recorded stack -- dev_helpers.hpp helper_stackid / _getstack
+    if (id == 27) return helper_stackid(maps, a2, a3, te, env.exact);
+    if (id == 67) return helper_getstack(a2, a3, a4, te, win, ml);
     // a QUEUE / STACK map: push / pop / peek, and lookup (a peek that returns
     // the slot), update (a push, the key ignored) and delete (a pop that
     // discards) -- dev_helpers.hpp helper_qs
@@ -72,6 +76,9 @@ __device__ __forceinline__ uint64_t call_helper(uint32_t id, uint64_t a1, uint64
     // an ARRAY_OF_MAPS: lookup yields the slot's fd, update / delete answer
     // -EINVAL (87 / 88 / 89: -ENOTSUP below) -- dev_helpers.hpp helper_mapinmap
     if (mt == MT_ARRAY_OF_MAPS && (id == 1 || id == 2 || id == 3)) return helper_mapinmap(maps, a1, a2, id);
+    // a STACK_TRACE: lookup yields a slot's frames, update answers -ENOTSUP,
+    // delete empties a slot -- dev_helpers.hpp helper_stmap
+    if (mt == MT_STACK_TRACE && (id == 1 || id == 2 || id == 3)) return helper_stmap(maps, a1, a2, id);
     // bpf_map_push / pop / peek_elem, and a Bloom filter's bpf_map_update_elem:
     // a push of the value, the key ignored
     const bool upd = id == 2 && mt == MT_BLOOM_FILTER;
@@ -854,6 +861,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(4))) void k_
     int32_t miss_fd;
     uint64_t miss_hash;
     uint32_t lru_ops;
+    uint32_t st_calls;
     bool ctx_ready;
     FastUnit fu;
     // the unit's addresses and per-unit helper state (also after the asm
@@ -885,6 +893,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(4))) void k_
       miss_fd = -1;
       miss_hash = 0;
       lru_ops = 0;
+      st_calls = 0;
       fu.vm = ncpu_pow2 ? (uint32_t)vcpu & (ncpu - 1) : (uint32_t)(vcpu % ncpu);
       fu.slot = slot;
       fu.len = len;
@@ -1176,6 +1185,9 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(4))) void k_
           te.trace_log = pin.trace_log;
           te.trace_cap = pin.trace_cap;
           te.unit = p.first_unit + unit;
+          te.stacks = pin.stacks;
+          te.stack_unit = unit;
+          te.st_calls = st_calls;
         }
         const uint64_t rv = call_helper<BIGSTACK>(c.call_id, R[1 * kBlock], R[2 * kBlock], R[3 * kBlock], R[4 * kBlock],
                                         R[5 * kBlock], p.maps, p.ncpu,
@@ -1184,6 +1196,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(4))) void k_
         miss_fd = env.miss_fd;
         miss_hash = env.miss_hash;
         lru_ops = env.lru_ops;
+        if constexpr (BIGSTACK) st_calls = te.st_calls;
         if (cerr != E_OK) {
           c.err = cerr;
           c.alive = false;

@@ -35,6 +35,7 @@ bool device_helper_supported(uint32_t id) {
     case 36:                      // bpf_probe_write_user
     case 125: case 160:           // bpf_ktime_get_boot_ns / _coarse_ns (helper 5's clock)
     case 25:                      // bpf_perf_event_output (a record in a software perf event's ring)
+    case 27: case 67:             // bpf_get_stackid / bpf_get_stack (the batch's recorded call stacks)
     case kTailHelper:
       return true;
   }
@@ -268,6 +269,8 @@ static int helper_arity(uint32_t id) {
     case 2: case 189: return 4;                // map_update_elem, xdp_load_bytes
     case kTailHelper: return 3;                // tail_call(ctx, prog_array, index)
     case 25: return 5;                         // perf_event_output(ctx, map, flags, data, size)
+    case 27: return 3;                         // get_stackid(ctx, map, flags)
+    case 67: return 4;                         // get_stack(ctx, buf, size, flags)
     case (uint32_t)kRetHelper: return 0;       // a linked tail-call target's exit
     default: return 5;                         // csum_diff and anything else
   }
@@ -522,6 +525,8 @@ int load_program(const RawInsn *code, size_t n, const std::map<size_t, size_t> &
       if (cur.imm == 6) out.trace_printk = true;
       // (helper_perf_output: beside them; the launch uploads the perf table first)
       if (cur.imm == 25) out.bloom = out.perf_output = true;
+      // (helper_stackid / helper_getstack: beside them)
+      if (cur.imm == 27 || cur.imm == 67) out.bloom = true;
       if (cur.imm == 58 || cur.imm == 187) out.sets_retval = true;
       // bpf_ktime_get_boot_ns / bpf_ktime_get_coarse_ns: a batch has one
       // clock source, so both are helper 5 from here on -- in the analyses,
@@ -548,11 +553,12 @@ int load_program(const RawInsn *code, size_t n, const std::map<size_t, size_t> &
           imm = lddw.map_by_fd((uint32_t)cur.imm);
           {  // a Bloom filter named by fd: helper 2 on it is a push; a QUEUE /
              // STACK: helpers 1 / 2 / 3 are peek / push / pop; an
-             // ARRAY_OF_MAPS: helper 1 yields a map fd
+             // ARRAY_OF_MAPS: helper 1 yields a map fd; a STACK_TRACE: helpers
+             // 1 / 2 / 3 are its own
             Runtime &r = rt();
             if (imm < kMaxFds && r.kind[imm] == HKind::MAP &&
                 (r.maps[imm].type == MT_BLOOM_FILTER || qs_type(r.maps[imm].type) ||
-                 r.maps[imm].type == MT_ARRAY_OF_MAPS))
+                 r.maps[imm].type == MT_ARRAY_OF_MAPS || r.maps[imm].type == MT_STACK_TRACE))
               out.bloom = true;
           }
           break;
@@ -938,12 +944,14 @@ static bool pointer_kinds(const std::vector<DInsn> &p, const std::vector<uint8_t
         // (a copy helper's destination of run-time length inside the ctx may
         // reach its packet pointers)
         if (writes_r1_helper(d.hi) && st[1].kind == P_CTX) ctx_written = true;
+        if (d.hi == 67 && st[2].kind == P_CTX) ctx_written = true;  // get_stack(ctx, buf, size, flags) writes r2's
         // (not of a QUEUE / STACK: the slot a peek returns is no element of a keyed value array;
         // not of an ARRAY_OF_MAPS: the result is a map handle, no pointer into
         // the outer map's storage -- every call through it has r1 unresolved,
-        // and what it reaches counts against every map)
+        // and what it reaches counts against every map; not of a STACK_TRACE:
+        // the frames of a slot are no element of a keyed value array either)
         st[0] = (d.hi == 1 && m.kind == P_MAPFD && map_rec(m.id) && !qs_type(map_rec(m.id)->type) &&
-                 map_rec(m.id)->type != MT_ARRAY_OF_MAPS)
+                 map_rec(m.id)->type != MT_ARRAY_OF_MAPS && map_rec(m.id)->type != MT_STACK_TRACE)
                     ? PVal{P_MVNULL, 0, m.id}
                     : kOther;
         break;
@@ -1087,6 +1095,7 @@ static void accesses(const std::vector<DInsn> &p, uint32_t i, const std::vector<
     case 28: arg(1); arg(3); return;
     case 130: arg(2); return;
     case 25: arg(4); return;  // perf_event_output reads r4's range (the ring is no map's value)
+    case 67: arg(2); return;  // get_stack writes r2's range (27: a map's slots, with the default below)
     case 132: case 133: arg(1); return;
     case 189: arg(3); return;
     // probe_read* / probe_read*_str write r1's range and read r3's; strncmp
@@ -1197,6 +1206,13 @@ static void const_loads(const std::vector<DInsn> &p, const std::vector<uint8_t> 
           case 16: case 36:  // get_current_comm(buf, ...), probe_write_user(dst, ...)
             writes.push_back(loc_of(p, st[1], 0, kUnknownLen));
             break;
+          case 67:  // get_stack(ctx, buf, size, flags) writes *buf
+            writes.push_back(loc_of(p, st[2], 0, kUnknownLen));
+            break;
+          case 27:  // get_stackid(ctx, map, flags): the slots of the map in r2
+            if (st[2].kind == P_MAPFD) writes.push_back(Loc{Loc::MAPVAL, st[2].id, 0, kUnknownLen});
+            else writes.push_back(Loc{Loc::ANY, -1, 0, 0});
+            break;
           case 182:  // strncmp: reads only
             break;
           default:
@@ -1293,13 +1309,15 @@ static void lpm_write_sites(const std::vector<DInsn> &p, const std::vector<uint8
 static void qs_call_sites(const std::vector<DInsn> &p, const std::vector<uint8_t> &lddw_src,
                           const std::vector<std::vector<PVal>> *in, FastForm &out) {
   const uint32_t n = (uint32_t)p.size();
-  std::vector<int32_t> named;
+  std::vector<int32_t> named, named_st;
   for (uint32_t i = 0; i < n; i++) {
     if (p[i].op != X_LDDW || i >= lddw_src.size() || lddw_src[i] != 1) continue;
     const uint64_t v = (uint64_t)(uint32_t)p[i].imm | ((uint64_t)(uint32_t)p[i].hi << 32);
     const MapRec *m = v < kMaxFds ? map_rec((int64_t)v) : nullptr;
     if (m && qs_type(m->type) && std::find(named.begin(), named.end(), (int32_t)v) == named.end())
       named.push_back((int32_t)v);
+    if (m && m->type == MT_STACK_TRACE && std::find(named_st.begin(), named_st.end(), (int32_t)v) == named_st.end())
+      named_st.push_back((int32_t)v);
   }
   std::vector<bool> is_target(n, false);
   for (uint32_t i = 0; i < n; i++) {
@@ -1317,6 +1335,20 @@ static void qs_call_sites(const std::vector<DInsn> &p, const std::vector<uint8_t
       use_def(p[j], u, df);
       if (!(df & (1u << reg))) continue;
       return p[j].op == X_MOV && !(p[j].aux & A_SRCREG) && p[j].imm == 0;
+    }
+    return false;
+  };
+  // bpf_get_stackid's flags (r3): a constant -- `mov r, imm` or a plain lddw
+  // under the same rule -- with BPF_F_REUSE_STACKID (bit 10) clear
+  auto no_reuse_before = [&](uint32_t call, int reg) {
+    for (uint32_t j = call; j-- > 0;) {
+      if (is_target[j + 1]) return false;
+      RegSet u, df;
+      use_def(p[j], u, df);
+      if (!(df & (1u << reg))) continue;
+      const bool k = (p[j].op == X_MOV && !(p[j].aux & A_SRCREG)) ||
+                     (p[j].op == X_LDDW && j < lddw_src.size() && lddw_src[j] == 0);
+      return k && !((uint32_t)p[j].imm & (uint32_t)kStReuse);
     }
     return false;
   };
@@ -1382,6 +1414,20 @@ static void qs_call_sites(const std::vector<DInsn> &p, const std::vector<uint8_t
     if (p[i].op != X_CALL) continue;
     const uint32_t h = (uint32_t)p[i].hi;
     const bool elem = h == 87 || h == 88 || h == 89;
+    // STACK_TRACE sites (FastForm::st_sites): 27 names its map in r2
+    if (h == 27 || h == 1 || h == 2 || h == 3) {
+      const int mr = h == 27 ? 2 : 1;
+      const bool fok = h == 27 ? no_reuse_before(i, 3) : true;
+      const bool dead = in && (*in)[i][1].kind == P_UNDEF && (*in)[i][0].kind == P_UNDEF;
+      if (!dead && in && !at[i].empty() && !at[i][mr].top) {
+        for (const int32_t fd : at[i][mr].fds) {
+          const MapRec *m = map_rec(fd);
+          if (m && m->type == MT_STACK_TRACE) out.st_sites.push_back({h, fd, fok});
+        }
+      } else if (!dead) {
+        for (const int32_t fd : named_st) out.st_sites.push_back({h, fd, fok});
+      }
+    }
     if (!elem && h != 1 && h != 2 && h != 3) continue;
     const bool flags0 = h == 87 ? zero_before(i, 3) : h == 2 ? zero_before(i, 4) : true;
     if (in) {
@@ -1453,6 +1499,8 @@ static void tail_save_masks(const std::vector<DInsn> &p, const std::vector<std::
       case 182: break;  // strncmp: reads only
       case 6: case 15: case 125: case 160: break;  // trace_printk reads only; no arguments
       case 25: break;  // perf_event_output reads only
+      case 27: break;  // get_stackid writes a map's slot only
+      case 67: write(st[2], 0, 1 << 16); break;  // get_stack(ctx, buf, size, flags) writes *buf
       default:
         if (d.hi != kRetHelper) {
           cm = 0x3f;
@@ -1572,6 +1620,17 @@ static void map_effects(const std::vector<DInsn> &prog, const std::vector<std::v
             if (t4 != -2) mark(t4, FX_READ);
             break;
           }
+          case 27:
+            // get_stackid(ctx, map, flags): the map handle is r2 -- a write of
+            // the STACK_TRACE map it names (which stack a slot keeps is an
+            // effect of the order), of every map when the kinds cannot place r2
+            mark(st[2].kind == P_MAPFD ? st[2].id : -1, FX_WRITE);
+            break;
+          case 67: {  // get_stack(ctx, buf, size, flags): writes through r2
+            const int32_t t2 = target(i, st[2], 0, 1);
+            if (t2 != -2) mark(t2, FX_WRITE);
+            break;
+          }
           case 6: {  // trace_printk reads the format and what its %s arguments point to
             for (int r : {1, 3, 4, 5}) {
               const int32_t t = target(i, st[r], 0, 1);
@@ -1664,8 +1723,9 @@ void build_fast(const LoadOut &lo, bool xdp, FastForm &out) {
   for (size_t i = 0; kinds_ok && i < prog.size(); i++) {
     const DInsn &d = prog[i];
     const bool copies = d.op == X_CALL && writes_r1_helper(d.hi);  // (writes through r1)
-    if (d.op != X_ST && d.op != X_STX && d.op != X_RMW_ADD && d.op != X_ATOMIC && !copies) continue;
-    const uint8_t k = in[i][copies ? 1 : d.dst].kind;
+    const bool copies2 = d.op == X_CALL && d.hi == 67;              // (get_stack: through r2)
+    if (d.op != X_ST && d.op != X_STX && d.op != X_RMW_ADD && d.op != X_ATOMIC && !copies && !copies2) continue;
+    const uint8_t k = in[i][copies ? 1 : copies2 ? 2 : d.dst].kind;
     if (k != P_UNDEF && k != P_STK && k != P_MAPVAL && k != P_CONST) out.stores_unit = true;
   }
   if (!kinds_ok) {

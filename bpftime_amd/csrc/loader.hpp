@@ -77,6 +77,17 @@ struct FastForm {
     bool flags0;
   };
   std::vector<QsSite> qs_sites;
+  // call sites that may reach a STACK_TRACE map: bpf_get_stackid (27, the map
+  // in r2) and helpers 1 / 2 / 3 (r1), resolved as QsSite::fd is.  flags_ok: a
+  // 27 whose flags register (r3) is a proven constant with BPF_F_REUSE_STACKID
+  // clear.  A parallel launch needs every 27 site flags_ok and no 1 / 3 site
+  // (vm_api.cpp st_launch_check); 27 sites name the maps k_stack_commit visits
+  struct StSite {
+    uint32_t helper;
+    int32_t fd;
+    bool flags_ok;
+  };
+  std::vector<StSite> st_sites;
   // the ARRAY_OF_MAPS maps the program names in an lddw.  The inner maps a
   // lookup on one yields are named by no lddw: before a launch the host walks
   // the slots of these maps (vm_api.cpp inner_launch_check)

@@ -39,7 +39,7 @@ long map_no_pop(MapRec &, void *);
 long map_no_peek(MapRec &, void *);
 const MapOps *map_ops(uint32_t type);  // nullptr: no such map type
 extern const MapOps kArrayOps, kPercpuArrayOps, kHashOps, kPercpuHashOps, kLruHashOps, kLpmTrieOps, kProgArrayOps,
-    kRingbufOps, kBloomFilterOps, kQueueOps, kStackOps, kArrayOfMapsOps, kPerfEventArrayOps;
+    kRingbufOps, kBloomFilterOps, kQueueOps, kStackOps, kArrayOfMapsOps, kPerfEventArrayOps, kStackTraceOps;
 
 // the one lookup buffer of a thread, shared by every map type
 extern thread_local std::vector<uint8_t> tl_lookup_buf;
@@ -115,6 +115,9 @@ int arrmaps_pull(MapRec &m);
 
 // map_perfarr.cpp: a new PERF_EVENT_ARRAY map's slots in the arena set to -1
 int perfarr_init(MapRec &m);
+
+// map_stacktrace.cpp: a new STACK_TRACE map's claim words in the arena set to "none"
+int stacktrace_init(MapRec &m);
 
 // map_lpm.cpp: the LPM half of Runtime::prepare_ix (its arguments; the caller
 // holds the runtime lock)

@@ -5,6 +5,7 @@
 //   array_map.cpp:19-81, fix_hash_map.cpp:16-84 + bpftime_hash_map.hpp,
 //   per_cpu_array_map.cpp:97-145, per_cpu_hash_map.cpp:141-216,
 //   map_in_maps.hpp (map_arrmaps.cpp), perf_event_array_map.cpp (map_perfarr.cpp),
+//   stack_trace_map.cpp (map_stacktrace.cpp),
 // with storage in one device arena (HBM) whose layout is described by the
 // DMap records the interpreter reads (csrc/common.hpp).  Host-side ops copy
 // the touched slots over PCIe: they are control-plane operations and must not
@@ -42,6 +43,7 @@ const MapOps *map_ops(uint32_t type) {
     case MT_STACK: return &kStackOps;
     case MT_ARRAY_OF_MAPS: return &kArrayOfMapsOps;
     case MT_PERF_EVENT_ARRAY: return &kPerfEventArrayOps;
+    case MT_STACK_TRACE: return &kStackTraceOps;
   }
   return nullptr;
 }
@@ -112,6 +114,7 @@ int bpftime_maps_create(int fd, const char *name, struct bpf_map_attr attr) {
     r.prog_gen++;
   }
   if (m.type == MT_PERF_EVENT_ARRAY && perfarr_init(m) < 0) return -1;  // every slot -1
+  if (m.type == MT_STACK_TRACE && stacktrace_init(m) < 0) return -1;    // every slot unclaimed
   if (m.lpm) {  // empty replica: root = -1, no nodes or entries, the pool's capacity
     const uint32_t hdr[4] = {~0u, 0, 0, m.lpm->cap};
     if (hipMemcpy((void *)base, hdr, 16, hipMemcpyHostToDevice) != hipSuccess) return -1;

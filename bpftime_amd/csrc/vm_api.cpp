@@ -63,6 +63,8 @@ static int trace_log_ensure() {
 }
 extern "C" hipError_t bpftime_amd_launch_interp(const KParams *p, uint32_t kind, bool big_stack, uint32_t grid,
                                                 uint32_t ordered, uint32_t block, hipStream_t stream);
+extern "C" hipError_t bpftime_amd_launch_stack_commit(const DMap *m, const StackSrc *src, uint64_t first_unit,
+                                                      uint64_t count, hipStream_t stream);
 
 // QUEUE / STACK maps in a launch of the program form `f` (loader.cpp
 // qs_call_sites).  The device's parallel push / pop / peek are correct only
@@ -144,6 +146,48 @@ static bool qs_launch_fence(bool adds, bool takes) {
     if (hipDeviceSynchronize() != hipSuccess) return false;
     r.qs_adder_inflight = false;
     r.qs_taker_inflight = false;
+  }
+  return true;
+}
+
+// STACK_TRACE maps in a launch of the program form `f` (loader.cpp
+// qs_call_sites, FastForm::st_sites).  Every batch: a map the program names must
+// hold the batch's deepest stack (value_size / 8 >= stack_max_depth).  A
+// parallel batch leaves the map as the reference's serial run would only
+// while a filled slot never changes (dev_helpers.hpp helper_stackid,
+// stack_commit.hip): BPF_F_REUSE_STACKID makes the stored stack depend on the
+// order of the calls, and a program-side lookup or delete would see or undo a
+// fill that is not stored yet.  Such programs run only in EBPF_BATCH_ORDERED
+// batches.  `commit`: the maps a parallel launch's bpf_get_stackid may claim
+// slots of, which k_stack_commit visits afterwards.
+static bool st_launch_check(const FastForm &f, bool ordered, uint32_t max_depth, std::string &error,
+                            std::vector<int32_t> &commit) {
+  commit.clear();
+  if (f.st_sites.empty()) return true;
+  Runtime &r = rt();
+  static const char *const kRule =
+      ": in a parallel batch a STACK_TRACE map only takes bpf_get_stackid calls whose flags are a proven constant "
+      "without BPF_F_REUSE_STACKID; this program runs only in EBPF_BATCH_ORDERED batches";
+  for (const FastForm::StSite &q : f.st_sites) {
+    if (q.fd < 0 || q.fd >= (int32_t)kMaxFds || r.kind[q.fd] != HKind::MAP || r.maps[q.fd].type != MT_STACK_TRACE)
+      continue;  // closed since the load: the device answers -EINVAL / NULL
+    const MapRec &m = r.maps[q.fd];
+    if (m.value_size / 8 < max_depth) {
+      error = "STACK_TRACE map fd " + std::to_string(q.fd) + " holds " + std::to_string(m.value_size / 8) +
+              " frames per stack (value_size / 8) < stack_max_depth " + std::to_string(max_depth);
+      return false;
+    }
+    if (ordered) continue;
+    const std::string at = " on STACK_TRACE map fd " + std::to_string(q.fd);
+    if (q.helper == 1 || q.helper == 3) {
+      error = std::string(q.helper == 1 ? "bpf_map_lookup_elem" : "bpf_map_delete_elem") + at + kRule;
+      return false;
+    }
+    if (q.helper == 27 && !q.flags_ok) {
+      error = "bpf_get_stackid" + at + " with flags not proven free of BPF_F_REUSE_STACKID" + kRule;
+      return false;
+    }
+    if (q.helper == 27 && std::find(commit.begin(), commit.end(), q.fd) == commit.end()) commit.push_back(q.fd);
   }
   return true;
 }
@@ -781,6 +825,24 @@ int Mi355xVm::exec_batch(const ebpf_batch *b) {
       }
     }
   }
+  // the recorded call stacks (include/ebpf-vm.h): any ctx kind
+  if (b->stack_arr) {
+    std::string bad;
+    if ((uintptr_t)b->stack_arr % 8 != 0)
+      bad = "stack_arr: an 8-aligned array";
+    else if (b->stack_unit_stride == 0 || b->stack_unit_stride % 8 != 0)
+      bad = "stack_unit_stride " + std::to_string(b->stack_unit_stride) + ": a nonzero multiple of 8";
+    else if (b->stack_frame_stride == 0 || b->stack_frame_stride % 8 != 0)
+      bad = "stack_frame_stride " + std::to_string(b->stack_frame_stride) + ": a nonzero multiple of 8";
+    else if ((uintptr_t)b->stack_depths % 4 != 0)
+      bad = "stack_depths: a 4-aligned array";
+    else if (b->stack_max_depth < 1 || b->stack_max_depth > kStMaxDepth)
+      bad = "stack_max_depth " + std::to_string(b->stack_max_depth) + ": 1.." + std::to_string(kStMaxDepth);
+    if (!bad.empty()) {
+      error = bad;
+      return -1;
+    }
+  }
   hipStream_t s = (hipStream_t)b->stream;
   if (b->count == 0) return 0;
   Runtime &r = rt();
@@ -798,6 +860,15 @@ int Mi355xVm::exec_batch(const ebpf_batch *b) {
   // ARRAY_OF_MAPS: the inner maps the slots name, before anything is queued
   if (!inner_launch_check(kind == CTX_XDP ? im.fx : im.fr, error)) return -1;
   if (!perf_launch_prepare(im.prog, error)) return -1;
+  // STACK_TRACE maps: what a parallel batch may do to one, and the maps
+  // k_stack_commit visits behind it
+  std::vector<int32_t> st_commit;
+  {
+    std::lock_guard<std::mutex> g(r.mu);
+    if (!st_launch_check(kind == CTX_XDP ? im.fx : im.fr, (b->flags & EBPF_BATCH_ORDERED) != 0,
+                         b->stack_arr ? b->stack_max_depth : 0, error, st_commit))
+      return -1;
+  }
   // the unwind helper as the device knows helpers (bpftime ids): the
   // registration that was given ubpf id unwind_idx
   int32_t unwind_helper = -1;
@@ -864,6 +935,9 @@ int Mi355xVm::exec_batch(const ebpf_batch *b) {
     p.kt_base = (const uint8_t *)b->ktime_arr;
     p.kt_stride = b->ktime_stride;
   }
+  if (b->stack_arr)
+    p.stacks = StackSrc{(const uint8_t *)b->stack_arr, b->stack_unit_stride, b->stack_frame_stride, b->stack_depths,
+                        b->stack_fixed_depth, b->stack_max_depth};
   p.pid_tgid = ((uint64_t)(uint32_t)getpid() << 32) | (uint32_t)syscall(SYS_gettid);
   task_into(p.task_uid_gid, p.task_comm);
   p.trace_log = trace_log().d;  // (made at load when the program calls helper 6)
@@ -1293,6 +1367,18 @@ int Mi355xVm::exec_batch(const ebpf_batch *b) {
     hipMemcpy(&bad, p.miss_counts + (uint64_t)grid * kMissParts, 4, hipMemcpyDeviceToHost);
     if (bad) fprintf(stderr, "bpftime_amd: k_miss_merge: %u records outside the windows\n", bad);
   }
+  // a parallel batch's bpf_get_stackid claims become stored stacks (without
+  // a stack source no call claims anything)
+  if (p.stacks.arr)
+    for (const int32_t fd : st_commit) {
+      if (e != hipSuccess) break;
+      DMap dm;
+      {
+        std::lock_guard<std::mutex> g(r.mu);
+        dm = r.maps[fd].d;
+      }
+      e = step("k_stack_commit", bpftime_amd_launch_stack_commit(&dm, &p.stacks, b->first_unit, b->count, s));
+    }
   if (e == hipSuccess && timed) e = hipEventRecord(ev_t1, s);
   if (e != hipSuccess) {
     error = std::string("kernel launch failed: ") + hipGetErrorString(e);
@@ -1736,7 +1822,8 @@ int bpftime_amd_register_default_helpers(struct ebpf_vm *vm) {
            {115, "bpf_probe_read_kernel_str"}, {182, "bpf_strncmp"},
            {15, "bpf_get_current_uid_gid"},  {16, "bpf_get_current_comm"},
            {36, "bpf_probe_write_user"},     {125, "bpf_ktime_get_boot_ns"},
-           {160, "bpf_ktime_get_coarse_ns"}, {25, "bpf_perf_event_output"}};
+           {160, "bpf_ktime_get_coarse_ns"}, {25, "bpf_perf_event_output"},
+           {27, "bpf_get_stackid"},          {67, "bpf_get_stack"}};
   int err = 0;
   for (auto &e : h) err |= ebpf_register(vm, e.id, e.name, nullptr);
   // ... and bpf_trace_printk once the host enabled it (bpftime_amd_enable_trace_printk)

@@ -86,6 +86,15 @@ BPF_FUNC_probe_write_user = 36
 BPF_FUNC_ktime_get_boot_ns = 125
 BPF_FUNC_ktime_get_coarse_ns = 160
 BPF_FUNC_perf_event_output = 25
+BPF_FUNC_get_stackid = 27
+BPF_FUNC_get_stack = 67
+
+# bpf_get_stackid / bpf_get_stack flags (linux/bpf.h)
+BPF_F_SKIP_FIELD_MASK = 0xFF
+BPF_F_USER_STACK = 1 << 8
+BPF_F_FAST_STACK_CMP = 1 << 9
+BPF_F_REUSE_STACKID = 1 << 10
+BPF_F_USER_BUILD_ID = 1 << 11
 
 # map types (linux/bpf.h)
 BPF_MAP_TYPE_HASH = 1
@@ -94,6 +103,7 @@ BPF_MAP_TYPE_PROG_ARRAY = 3
 BPF_MAP_TYPE_PERF_EVENT_ARRAY = 4
 BPF_MAP_TYPE_PERCPU_HASH = 5
 BPF_MAP_TYPE_PERCPU_ARRAY = 6
+BPF_MAP_TYPE_STACK_TRACE = 7
 BPF_MAP_TYPE_LRU_HASH = 9
 BPF_MAP_TYPE_LPM_TRIE = 11
 BPF_MAP_TYPE_ARRAY_OF_MAPS = 12

@@ -20,7 +20,7 @@ import struct
 
 from .isa import (Asm, BPF_ANY, BPF_FUNC_get_current_pid_tgid, BPF_FUNC_ktime_get_ns, BPF_FUNC_map_lookup_elem,
                   BPF_FUNC_map_update_elem, BPF_FUNC_override_return, BPF_FUNC_set_retval,
-                  BPF_FUNC_ringbuf_output, BPF_FUNC_perf_event_output, BPF_NOEXIST, ATOMIC_ADD, XDP_DROP, XDP_PASS, XDP_TX, XDP_ABORTED)
+                  BPF_FUNC_ringbuf_output, BPF_FUNC_perf_event_output, BPF_FUNC_get_stackid, BPF_NOEXIST, ATOMIC_ADD, XDP_DROP, XDP_PASS, XDP_TX, XDP_ABORTED)
 
 ETH_P_IP_LE = 0x0008  # htons(0x0800) as read by a little-endian ldxh
 IPPROTO_TCP, IPPROTO_UDP = 6, 17
@@ -920,4 +920,23 @@ def ringbuf_emitter(rb_fd: int, size: int = 32) -> bytes:
     a = Asm()
     a.mov64(2, "r1").ld_map_fd(1, rb_fd).mov64(3, size).mov64(4, 0)
     a.call(BPF_FUNC_ringbuf_output)
+    return a.exit().assemble()
+
+
+# ---- BPF_MAP_TYPE_STACK_TRACE (bpf_get_stackid) ------------------------------
+def stack_count(stack_fd: int, counts_fd: int, flags: int = 1 << 8) -> bytes:
+    """Count events by call stack: id = bpf_get_stackid(ctx, stack map, flags)
+    on the unit's recorded stack, then counts[id] += 1 (an atomic u64 add);
+    a negative id, or one past counts' end, counts nothing.  r0 = the helper's
+    answer.  stack_fd: STACK_TRACE; counts_fd: ARRAY of u64, at least the
+    stack map's max_entries.  flags: BPF_F_USER_STACK (1 << 8) by default."""
+    a = Asm()
+    a.ld_map_fd(2, stack_fd).mov64(3, flags).call(BPF_FUNC_get_stackid)
+    a.mov64(6, "r0")
+    a.jmp("jslt", 0, 0, "out")
+    a.stx(4, 10, -4, 0)
+    a.mov64(2, "r10").add64(2, -4).ld_map_fd(1, counts_fd).call(BPF_FUNC_map_lookup_elem)
+    a.jmp("jeq", 0, 0, "out")
+    a.mov64(1, 1).atomic(8, ATOMIC_ADD, 0, 0, 1)
+    a.label("out").mov64(0, "r6")
     return a.exit().assemble()

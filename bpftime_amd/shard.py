@@ -13,6 +13,9 @@ shards:
   * queues / stacks    add-only use (every shard only pushes): the initial
                        elements, then each shard's appended elements in shard
                        order; any other use is order dependent and is rejected
+  * stack traces       union of the filled slots; a slot several shards filled
+                       keeps the lowest shard's stack (shards are contiguous,
+                       so that is the call a serial run would have let fill it)
 The array rule runs in libbpftime_amd (bpftime_amd_merge_delta).
 """
 from __future__ import annotations
@@ -115,6 +118,20 @@ def merge_queue_append(init: List[bytes], shards: List[List[bytes]], max_entries
         out.extend(sh[len(init):])
     if len(out) > max_entries:
         raise ValueError(f"merged queue / stack has {len(out)} elements > max_entries {max_entries}")
+    return out
+
+
+def merge_stack_traces(init: Dict[int, list], shards: List[Dict[int, list]]) -> Dict[int, list]:
+    """A STACK_TRACE map's shards, each {slot id: frames} (Map.stack_frames
+    over the ids), given in shard order; init: the slots filled before the
+    batch, which every shard started from.  A filled slot keeps its stack
+    (the launches carry no BPF_F_REUSE_STACKID), so the result is init, then
+    per slot the first shard that filled it: the call that reaches an empty
+    slot first in stream order."""
+    out = {int(k): list(v) for k, v in init.items()}
+    for sh in shards:
+        for k, v in sh.items():
+            out.setdefault(int(k), list(v))
     return out
 
 

@@ -301,6 +301,15 @@ class Map:
             out.append(bytes(raw[at:at + self.value_size]))
         return out
 
+    # BPF_MAP_TYPE_STACK_TRACE (stack_trace_map.cpp)
+    def stack_frames(self, id: int) -> Optional[list]:
+        """STACK_TRACE: the frames slot `id` holds (an empty stack is []);
+        None for an empty slot or an id past the end."""
+        cap = max(self.value_size // 8, 1)
+        out = (C.c_uint64 * cap)()
+        n = lib().bpftime_amd_stack_trace_get(self.fd, id, out, cap)
+        return None if n < 0 else [int(out[i]) for i in range(min(n, cap))]
+
     def bloom_seed(self, set: Optional[int] = None) -> int:
         """The filter's jhash seed; `set` installs a new one first, which
         zeroes the bit array."""
@@ -444,11 +453,18 @@ class VM:
                    len_out: Optional[DeviceBuffer] = None, flags: int = BATCH_SYNC, first_unit: int = 0,
                    head: int = 0, data_offset: int = 0, ifindex: int = 0, rxq: int = 0,
                    stream: int = 0, descs: Optional[DeviceBuffer] = None, umem_bytes: int = 0,
-                   sys_nr: Optional[int] = None, pid_tgid_off: int = 0, ktime_off: int = 0) -> int:
+                   sys_nr: Optional[int] = None, pid_tgid_off: int = 0, ktime_off: int = 0,
+                   stacks: Optional[DeviceBuffer] = None, stack_unit_stride: int = 0, stack_frame_stride: int = 0,
+                   stack_depths: Optional[DeviceBuffer] = None, stack_fixed_depth: int = 0,
+                   stack_max_depth: int = 0) -> int:
         """descs: AF_XDP descriptor mode ({u64 addr; u32 len; u32 options} per
         unit, frames at data + addr inside umem_bytes; stride = chunk size).
         pid_tgid_off / ktime_off: the recorded caller / clock of a syscall
-        replay unit (include/ebpf-vm.h)."""
+        replay unit (include/ebpf-vm.h).  stacks: the units' recorded call
+        stacks for bpf_get_stackid / bpf_get_stack (u64 frames; frame k of unit
+        i at i * stack_unit_stride + k * stack_frame_stride), stack_depths
+        (u32 per unit) or stack_fixed_depth their frame counts, stack_max_depth
+        the most frames a unit may have (1..127)."""
         b = EbpfBatch(ctx_kind=kind, flags=flags, count=count, data=data.ptr + data_offset, stride=stride,
                       lens=lens.ptr if lens else None, fixed_len=fixed_len, ingress_ifindex=ifindex,
                       rx_queue_index=rxq, head=head, verdicts=verdicts.ptr if verdicts else None,
@@ -457,7 +473,10 @@ class VM:
                       len_out=len_out.ptr if len_out else None, first_unit=first_unit,
                       stream=stream or None, descs=descs.ptr if descs else None, umem_bytes=umem_bytes,
                       sys_nr=-1 if sys_nr is None else sys_nr, pid_tgid_off=pid_tgid_off,
-                      ktime_off=ktime_off)
+                      ktime_off=ktime_off, stack_arr=stacks.ptr if stacks else None,
+                      stack_unit_stride=stack_unit_stride, stack_frame_stride=stack_frame_stride,
+                      stack_depths=stack_depths.ptr if stack_depths else None,
+                      stack_fixed_depth=stack_fixed_depth, stack_max_depth=stack_max_depth)
         if sys_nr is not None:
             b.flags |= BATCH_SYS_NR
         rc = lib().ebpf_exec_batch(C.c_void_p(self.h), C.byref(b))

@@ -271,6 +271,18 @@ int bpftime_amd_map_type_supported(uint32_t type);
  * array -- bits set under another seed mean nothing.  0, or -1 (not a Bloom
  * filter). */
 int bpftime_amd_bloom_seed(int fd, const uint32_t *set, uint32_t *out);
+/* STACK_TRACE (7, stack_trace_map.cpp): bpftime_maps_create needs key_size 4,
+ * value_size a multiple of 8 and max_entries > 0, else -1 + EINVAL.  Slot id
+ * holds the frames of the stack whose hash is id modulo max_entries, stored by
+ * a program's bpf_get_stackid from the batch's recorded stacks (ebpf-vm.h,
+ * ebpf_batch::stack_arr).  bpftime_map_lookup_elem returns value_size bytes --
+ * the frames, then zeros -- or NULL + ENOENT; update returns -ENOTSUP; delete 0
+ * or -1 + ENOENT; get_next_key -1 + ENOTSUP; a NULL key EINVAL.  Every host
+ * operation waits for the device first.  _stack_trace_get copies slot id's
+ * frames to out (at most cap) and returns the slot's frame count; -1 + ENOENT
+ * for an empty slot or an id past the end, -1 + EINVAL when fd is no
+ * STACK_TRACE map. */
+int bpftime_amd_stack_trace_get(int fd, uint32_t id, uint64_t *out, uint32_t cap);
 /* An LPM trie whose device update (ORDERED batch) ran out of the node pool
  * keeps the state from before that batch and reports ENOMEM on every host op
  * and every launch of a program naming a trie until this acknowledges it:

@@ -55,9 +55,9 @@ void ebpf_set_error_print(struct ebpf_vm *vm, int (*error_printf)(FILE *stream, 
  * 4 / 112 / 113 (probe_read / _user / _kernel), 6 (trace_printk, once bpftime_amd_enable_trace_printk(1)), 7
  * (get_prandom_u32), 8 (get_smp_processor_id), 12 (tail_call), 14
  * (get_current_pid_tgid), 15 (get_current_uid_gid), 16 (get_current_comm), 25
- * (perf_event_output), 28 (csum_diff), 36 (probe_write_user), 44 (xdp_adjust_head), 45 / 114 / 115
+ * (perf_event_output), 27 (get_stackid, over the batch's recorded stacks: ebpf_batch::stack_arr), 28 (csum_diff), 36 (probe_write_user), 44 (xdp_adjust_head), 45 / 114 / 115
  * (probe_read_str / _user_str / _kernel_str), 58 (override_return), 65
- * (xdp_adjust_tail), 87-89 (map push / pop / peek), 125 / 160
+ * (xdp_adjust_tail), 67 (get_stack, over the same stacks), 87-89 (map push / pop / peek), 125 / 160
  * (ktime_get_boot_ns / _coarse_ns), 130-133 (ringbuf output / reserve / submit /
  * discard), 182 (strncmp), 187 (set_retval) and 189 (xdp_load_bytes)
  * (loader.cpp device_helper_supported).  0 / -1. */
@@ -99,8 +99,9 @@ ebpf_jit_fn ebpf_load_aot_object(struct ebpf_vm *vm, const void *buf, size_t buf
 #define EBPF_BATCH_SYNC 0x1    /* wait for completion; return the failed-unit count */
 /* one lane, units in index order (exact sequential semantics).  The only batches that run a
  * program which mixes adding to, removing from and peeking one QUEUE / STACK map, pushes with
- * non-zero or unproven flags (BPF_EXIST), or writes an LPM trie: other batches of it are refused
- * at launch (bpftime_amd.h, bpftime_map_push_elem) */
+ * non-zero or unproven flags (BPF_EXIST), writes an LPM trie, calls bpf_get_stackid with flags
+ * not proven free of BPF_F_REUSE_STACKID, or looks up / deletes in a STACK_TRACE map: other
+ * batches of it are refused at launch (bpftime_amd.h, bpftime_map_push_elem) */
 #define EBPF_BATCH_ORDERED 0x2
 #define EBPF_BATCH_UNCHECKED 0x4 /* skip the global-window confinement check */
 #define EBPF_BATCH_SYS_NR 0x8    /* EBPF_CTX_SYSCALL: only records whose id == sys_nr run (per-syscall attach) */
@@ -163,6 +164,29 @@ struct ebpf_batch {
 	uint64_t pid_tgid_stride;
 	const void *ktime_arr;
 	uint64_t ktime_stride;
+	/* The units' recorded user call stacks: what bpf_get_stackid (27) and
+	 * bpf_get_stack (67) read where the reference asks the uprobe attach
+	 * implementation for the caller's stack (bpf_helper.cpp:791-893).  Frame k of
+	 * unit i (its index in this batch, whatever first_unit says) is the u64 at
+	 * stack_arr + i * stack_unit_stride + k * stack_frame_stride, so one row per
+	 * unit (unit stride = row bytes, frame stride 8) and frame-major arrays (unit
+	 * stride 8, frame stride = 8 * count: neighbouring lanes read neighbouring
+	 * words) both fit.  Unit i has stack_depths[i] frames, or stack_fixed_depth
+	 * when stack_depths is NULL; the device clamps every depth to stack_max_depth
+	 * (1..127), the most frames the arrays hold per unit.  A unit with depth 0 has
+	 * no stack (-ENOENT); stack_arr NULL: the batch has no stack source and both
+	 * helpers answer -ENOTSUP.  Any ctx kind.  A non-NULL stack_arr must be
+	 * 8-aligned with both strides nonzero multiples of 8, stack_depths 4-aligned
+	 * and stack_max_depth in 1..127, and every STACK_TRACE map the program names
+	 * must hold stack_max_depth frames (value_size / 8); else the batch fails
+	 * (-1, named).  bpftime_amd_syscall_dispatch_records / _soa pass no stacks:
+	 * the helpers answer -ENOTSUP there. */
+	const void *stack_arr;
+	uint64_t stack_unit_stride;
+	uint64_t stack_frame_stride;
+	const uint32_t *stack_depths;
+	uint32_t stack_fixed_depth;
+	uint32_t stack_max_depth;
 };
 
 /* linux/if_xdp.h struct xdp_desc */
