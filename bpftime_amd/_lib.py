@@ -49,6 +49,13 @@ class SysRecords(C.Structure):  # include/bpftime_amd.h struct bpftime_amd_sys_r
     _fields_ = [("enter", C.c_void_p), ("exit", C.c_void_p), ("clock", C.c_void_p), ("count", C.c_uint64)]
 
 
+class CallRecords(C.Structure):  # include/bpftime_amd.h struct bpftime_amd_call_records
+    _fields_ = [("enter", C.c_void_p), ("leave", C.c_void_p), ("func", C.c_void_p), ("pid_tgid", C.c_void_p),
+                ("clock", C.c_void_p), ("stack_arr", C.c_void_p), ("stack_unit_stride", C.c_uint64),
+                ("stack_frame_stride", C.c_uint64), ("stack_depths", C.c_void_p),
+                ("stack_fixed_depth", C.c_uint32), ("stack_max_depth", C.c_uint32), ("count", C.c_uint64)]
+
+
 class PerfEvent(C.Structure):
     """struct bpftime_amd_perf_event (include/bpftime_amd.h)"""
     _fields_ = [("type", C.c_int), ("pid", C.c_int), ("enabled", C.c_int), ("tracepoint_id", C.c_int32),
@@ -154,6 +161,15 @@ SIGNATURES = [
     ("bpftime_amd_ringbuf_fetch", C.c_int64, [C.c_int, C.c_void_p, C.c_uint64, u64p]),
     ("bpftime_amd_vm_set_task", C.c_int, [C.c_void_p, C.c_char_p, u64p]),
     ("bpftime_amd_vm_get_task", C.c_int, [C.c_void_p, C.c_char_p, u64p]),
+    ("bpftime_amd_vm_set_attach", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
+    ("bpftime_attach_perf_to_bpf_with_cookie", C.c_int, [C.c_int, C.c_int, C.c_uint64]),
+    ("bpftime_amd_uprobe_attach", C.c_int, [C.c_int, C.c_uint64, C.c_int, u64p]),
+    ("bpftime_amd_uprobe_attach_link", C.c_int, [C.c_int, C.c_uint64]),
+    ("bpftime_amd_uprobe_link_bound", C.c_int, [C.c_int]),
+    ("bpftime_amd_uprobe_detach", C.c_int, [C.c_int]),
+    ("bpftime_amd_uprobe_dispatch", C.c_int64, [C.POINTER(CallRecords), C.c_void_p, C.c_void_p, C.c_uint32,
+                                                C.c_void_p]),
+    ("bpftime_amd_uprobe_last_ms", C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), u64p]),
     ("bpftime_amd_enable_trace_printk", C.c_int, [C.c_int]),
     ("bpftime_amd_trace_read", C.c_int64, [C.POINTER(TraceLine), C.c_uint64, C.c_void_p, C.c_uint64, u64p]),
     ("bpftime_amd_syscall_attach", C.c_int, [C.c_int, C.c_int64]),

@@ -386,6 +386,9 @@ constexpr uint32_t CTX_RAW = 0;      // r1 = unit memory, r2 = length
 constexpr uint32_t CTX_XDP = 1;      // r1 = xdp_md_userspace (48 B, LDS)
 constexpr uint32_t CTX_SYSCALL = 2;  // r1 = trace_event_raw_sys_enter (64 B) or, for
                                      // EBPF_CTX_SYSCALL_EXIT batches, trace_event_raw_sys_exit (24 B)
+// (EBPF_CTX_UPROBE batches run as CTX_RAW: r1 = the unit, a struct pt_regs,
+// r2 = its size)
+constexpr uint32_t kPtRegsBytes = 168;  // x86-64 struct pt_regs: 21 u64
 
 // Launches of at least this many units build the flat table of an IPv4 LPM
 // trie changed since the last one (map_lpm.cpp lpm_prepare_launch); smaller ones walk
@@ -497,6 +500,11 @@ struct KParams {
   // the units' recorded call stacks (bpf_get_stackid / bpf_get_stack), indexed
   // by the unit's index in the batch; read like the identity above
   StackSrc stacks;
+  // the running attachment (bpf_get_func_ip / bpf_get_attach_cookie): the
+  // probed function's address (0: none, or an override callback) and the
+  // attachment's cookie (0: none); read like the identity above
+  uint64_t attach_func_ip;
+  uint64_t attach_cookie;
 };
 
 // Where a syscall replay's fields live (include/bpftime_amd.h): record i's
@@ -573,6 +581,7 @@ struct SeqParams {
   uint8_t *trace_log;     // bpf_trace_printk's record log (trace_fmt.hpp), or null
   uint64_t trace_cap;
   SeqTask tasks[kSeqMaxTasks];
+  uint64_t cookies[kSeqMaxProgs];  // progs[a]'s attach cookie (bpf_get_attach_cookie; 0: none)
 };
 static_assert(sizeof(SeqParams) <= 4096, "kernel arguments");
 

@@ -1514,6 +1514,11 @@ struct TaskEnv {
   // out-of-line helpers by address: a field more there grew the scratch frame
   // of two LDS-stack instances of k_interp
   uint32_t st_calls;
+  // the running attachment's probed function and cookie (bpf_get_func_ip /
+  // bpf_get_attach_cookie, bpf_helper.cpp:684-700): launch constants like the
+  // identity (KParams::attach_*; the cookie per attached program in SeqParams)
+  uint64_t func_ip;
+  uint64_t cookie;
 };
 
 // bpf_get_current_comm(buf, size) = strncpy(buf, comm, size): comm up to and

@@ -27,7 +27,7 @@ int bpftime_progs_create(int fd, const void *insns, size_t insn_cnt, const char 
   return fd;
 }
 
-static int link_perf(int fd, int prog_fd, int perf_fd, int bad_errno);
+static int link_perf(int fd, int prog_fd, int perf_fd, int bad_errno, const uint64_t *cookie = nullptr);
 
 // bpftime_shm_internal.cpp:566-607: only prog_fd is validated; the target of
 // an XDP link is an ifindex.
@@ -37,7 +37,9 @@ int bpftime_link_create(int fd, struct bpf_link_create_args *args) {
     // :578-600: a perf-event link's target must be a perf event (libbpf
     // probes with target_fd -1 and expects EBADF); it attaches like
     // BPF_PROG_ATTACH (both fds checked under the runtime lock, link_perf)
-    return link_perf(fd, (int)args->prog_fd, (int)args->target_fd, EBADF);
+    // (the cookie: perf_event.bpf_cookie, the first word of the union --
+    // link_handler.hpp:25-31; the other attach types' unions hold none)
+    return link_perf(fd, (int)args->prog_fd, (int)args->target_fd, EBADF, &args->attach_union[0]);
   }
   std::lock_guard<std::mutex> g(r.mu);
   if (!args) {
@@ -303,8 +305,9 @@ static int perf_drives(const PerfRec &p, int64_t *nr, int *enter) {
 // add_bpf_link / add_bpf_prog_attach_target (bpftime_shm_internal.cpp:293-315,
 // :566-607) check only the handler kinds and resolve the id when its agent
 // attaches.  bad_errno: what a non-perf perf_fd or non-program prog_fd sets
-// (ENOENT for BPF_PROG_ATTACH, EBADF for BPF_LINK_CREATE).
-static int link_perf(int fd, int prog_fd, int perf_fd, int bad_errno) {
+// (ENOENT for BPF_PROG_ATTACH, EBADF for BPF_LINK_CREATE).  cookie: the link's
+// attach cookie (null: none), handed to the syscall attachment it drives.
+static int link_perf(int fd, int prog_fd, int perf_fd, int bad_errno, const uint64_t *cookie) {
   Runtime &r = rt();
   int64_t nr = -1;
   int drives, enter = 1;
@@ -328,6 +331,7 @@ static int link_perf(int fd, int prog_fd, int perf_fd, int bad_errno) {
   if (drives > 0) {
     id = bpftime_amd_syscall_attach_ex(prog_fd, nr, enter);  // instantiates the program (outside the lock)
     if (id < 0) return -1;
+    if (cookie) syscall_attach_set_cookie(id, *cookie);
   }
   std::lock_guard<std::mutex> g(r.mu);
   fd = alloc_fd(fd);
@@ -341,12 +345,18 @@ static int link_perf(int fd, int prog_fd, int perf_fd, int bad_errno) {
   l.attach_type = BPFTIME_AMD_BPF_PERF_EVENT;
   l.perf = true;
   l.attach_id = id;
+  l.has_cookie = cookie != nullptr;
+  l.cookie = cookie ? *cookie : 0;
   r.links[fd] = l;
   r.kind[fd] = HKind::LINK;
   return fd;
 }
 
 int bpftime_attach_perf_to_bpf(int perf_fd, int bpf_fd) { return link_perf(-1, bpf_fd, perf_fd, ENOENT); }
+
+int bpftime_attach_perf_to_bpf_with_cookie(int perf_fd, int bpf_fd, uint64_t cookie) {
+  return link_perf(-1, bpf_fd, perf_fd, ENOENT, &cookie);
+}
 
 int bpftime_amd_link_perf(int fd, int prog_fd, int perf_fd) { return link_perf(fd, prog_fd, perf_fd, ENOENT); }
 

@@ -54,6 +54,10 @@ __device__ __forceinline__ uint64_t call_helper(uint32_t id, uint64_t a1, uint64
     if (id == 15) return te.uid_gid;
     if (id == 16) return helper_comm(a1, a2, te, win, ml);
     if (id == 6) return helper_trace(a1, a2, a3, a4, a5, te, win, ml);
+    // bpf_get_func_ip / bpf_get_attach_cookie (bpf_helper.cpp:684-700): the
+    // running attachment's, launch constants beside the identity
+    if (id == 173) return te.func_ip;
+    if (id == 174) return te.cookie;
     // bpf_probe_read* / bpf_probe_read_*_str / bpf_strncmp: byte ranges of
     // run-time length, checked against the windows and the lane's own stack
     // and ctx extents -- dev_helpers.hpp helper_mem
@@ -1188,6 +1192,8 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(4))) void k_
           te.stacks = pin.stacks;
           te.stack_unit = unit;
           te.st_calls = st_calls;
+          te.func_ip = pin.attach_func_ip;
+          te.cookie = pin.attach_cookie;
         }
         const uint64_t rv = call_helper<BIGSTACK>(c.call_id, R[1 * kBlock], R[2 * kBlock], R[3 * kBlock], R[4 * kBlock],
                                         R[5 * kBlock], p.maps, p.ncpu,
@@ -1686,6 +1692,8 @@ __global__ __launch_bounds__(kBlock) void k_sys_seq(SeqParams p) {
             te.trace_cap = p.trace_cap;
             te.unit = idx;
           }
+          // its cookie (a syscall tracepoint probes no function: func_ip 0)
+          if (cid == 174) te.cookie = p.cookies[__builtin_amdgcn_readfirstlane((uint32_t)a) % kSeqMaxProgs];
           const uint64_t rv = cid == kTailHelper ? 0
                               : call_helper<true>(cid, R[1 * kBlock], R[2 * kBlock], R[3 * kBlock], R[4 * kBlock],
                                             R[5 * kBlock], p.maps, p.ncpu, idx ^ ((uint64_t)c.steps << 40), env,

@@ -36,6 +36,7 @@ bool device_helper_supported(uint32_t id) {
     case 125: case 160:           // bpf_ktime_get_boot_ns / _coarse_ns (helper 5's clock)
     case 25:                      // bpf_perf_event_output (a record in a software perf event's ring)
     case 27: case 67:             // bpf_get_stackid / bpf_get_stack (the batch's recorded call stacks)
+    case 173: case 174:           // bpf_get_func_ip / bpf_get_attach_cookie (the running attachment's)
     case kTailHelper:
       return true;
   }
@@ -55,7 +56,11 @@ static bool mem_helper(int64_t id) { return mem_copy_helper(id) || id == 182; }
 // r2's; get_current_comm(buf, size) writes r1's; trace_printk(fmt, fmt_size,
 // a3, a4, a5) reads r1's and, for a %s, what r3..r5 point to;
 // get_current_uid_gid takes nothing
-static bool task_trace_helper(int64_t id) { return id == 6 || id == 15 || id == 16 || id == 36; }
+// ... and get_func_ip / get_attach_cookie, launch constants that travel with
+// the identity (dev_helpers.hpp TaskEnv): no arguments
+static bool task_trace_helper(int64_t id) {
+  return id == 6 || id == 15 || id == 16 || id == 36 || id == 173 || id == 174;
+}
 // the helpers that write a range of run-time length through r1
 static bool writes_r1_helper(int64_t id) { return mem_copy_helper(id) || id == 16 || id == 36; }
 
@@ -259,6 +264,7 @@ static int helper_arity(uint32_t id) {
   switch (id) {
     case 5: case 7: case 8: return 0;          // ktime_get_ns, get_prandom_u32, get_smp_processor_id
     case 15: case 125: case 160: return 0;     // get_current_uid_gid, ktime_get_boot_ns / _coarse_ns
+    case 173: case 174: return 0;              // get_func_ip / get_attach_cookie: launch constants (ctx unread)
     case 16: return 2;                         // get_current_comm(buf, size)
     case 36: return 3;                         // probe_write_user(dst, src, len)
     case 1: case 3: case 44: case 65: return 2;  // map_lookup/delete_elem, xdp_adjust_head/tail
@@ -526,7 +532,7 @@ int load_program(const RawInsn *code, size_t n, const std::map<size_t, size_t> &
       // (helper_perf_output: beside them; the launch uploads the perf table first)
       if (cur.imm == 25) out.bloom = out.perf_output = true;
       // (helper_stackid / helper_getstack: beside them)
-      if (cur.imm == 27 || cur.imm == 67) out.bloom = true;
+      if (cur.imm == 27 || cur.imm == 67) out.bloom = out.reads_stacks = true;
       if (cur.imm == 58 || cur.imm == 187) out.sets_retval = true;
       // bpf_ktime_get_boot_ns / bpf_ktime_get_coarse_ns: a batch has one
       // clock source, so both are helper 5 from here on -- in the analyses,
@@ -1080,6 +1086,7 @@ static void accesses(const std::vector<DInsn> &p, uint32_t i, const std::vector<
   switch (id) {
     case 5: case 7: case 8: case 131: case 44: case 65: return;  // no memory (ctx helpers: unit-local)
     case 15: case 125: case 160: return;  // the VM's identity, the clock: no memory
+    case 173: case 174: return;           // the attachment's function address / cookie: no memory
     case 16: arg(1); return;              // get_current_comm writes r1's range
     case 36: arg(1); arg(2); return;      // probe_write_user(dst, src, len)
     // trace_printk reads the format and what a %s argument points to: r3..r5
@@ -1190,6 +1197,7 @@ static void const_loads(const std::vector<DInsn> &p, const std::vector<uint8_t> 
           case 1: case 5: case 7: case 8: case 14: case 28: case 58: case 187: case 130:
           case 131: case 132: case 133: case 44: case 65:
           case 6: case 15: case 125: case 160:  // (trace_printk reads only, into the log)
+          case 173: case 174:                   // (launch constants)
           case 25:                              // (perf_event_output reads only, into a ring)
             break;  // no array-map writes (ring memory, the unit's ctx, dispatch state)
           case 88: case 89:  // pop / peek of a QUEUE / STACK write *value
@@ -1498,6 +1506,7 @@ static void tail_save_masks(const std::vector<DInsn> &p, const std::vector<std::
         break;
       case 182: break;  // strncmp: reads only
       case 6: case 15: case 125: case 160: break;  // trace_printk reads only; no arguments
+      case 173: case 174: break;  // get_func_ip / get_attach_cookie: launch constants
       case 25: break;  // perf_event_output reads only
       case 27: break;  // get_stackid writes a map's slot only
       case 67: write(st[2], 0, 1 << 16); break;  // get_stack(ctx, buf, size, flags) writes *buf
@@ -1597,7 +1606,7 @@ static void map_effects(const std::vector<DInsn> &prog, const std::vector<std::v
           case 1: case 89: mark(fd, FX_READ); break;                    // map_lookup_elem, map_peek_elem
           case 2: case 3: case 130: case 131: case 87: case 88: mark(fd, FX_WRITE); break;  // update, delete, ringbuf output / reserve, push, pop
           case 5: case 7: case 8: case 14: case 28: case 44: case 58: case 65: case 132: case 133: case 187: case 189:
-          case 15: case 125: case 160:
+          case 15: case 125: case 160: case 173: case 174:
             break;  // no map effects (132 / 133 finish a reservation 131 marked)
           case 16: {  // get_current_comm writes through r1
             const int32_t t1 = target(i, st[1], 0, 1);

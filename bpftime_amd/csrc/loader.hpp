@@ -112,6 +112,7 @@ struct LoadOut {
   uint32_t comb_entries = 0;  // per-block LDS combining entries (0 = none needed)
   bool bloom = false;         // calls bpf_map_push / pop / peek_elem or names a BLOOM_FILTER / QUEUE / STACK / ARRAY_OF_MAPS, or calls a helper only they carry: scratch-stack kernels only
   bool perf_output = false;   // calls bpf_perf_event_output: the device's perf table is brought up to date before a launch
+  bool reads_stacks = false;  // calls bpf_get_stackid / bpf_get_stack: a dispatch gathers the units' recorded stacks
   bool trace_printk = false;  // calls bpf_trace_printk: the runtime's trace log must exist before a launch
   bool may_delete = false;    // calls map_delete_elem: hash lookup indexes stop being valid
   bool tail_call = false;     // calls bpf_tail_call: linked with the prog arrays' targets at launch

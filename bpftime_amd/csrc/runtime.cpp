@@ -107,7 +107,7 @@ int bpftime_is_perf_event_fd(int fd) { return fd >= 0 && fd < (int)kMaxFds && rt
 
 void bpftime_close(int fd) {
   Runtime &r = rt();
-  int detach = 0;
+  int detach = 0, udetach = 0;
   {
     std::lock_guard<std::mutex> g(r.mu);
     if (fd < 0 || fd >= (int)kMaxFds) return;
@@ -124,6 +124,7 @@ void bpftime_close(int fd) {
       r.progs[fd] = ProgRec();
     } else if (r.kind[fd] == HKind::LINK) {
       detach = r.links[fd].attach_id;
+      udetach = r.links[fd].uprobe_id;
       r.links[fd] = LinkRec();
     } else if (r.kind[fd] == HKind::PERF) {
       // (its ring goes with the record; the arena's bytes come back at reset)
@@ -133,6 +134,7 @@ void bpftime_close(int fd) {
     r.kind[fd] = HKind::NONE;
   }
   if (detach) bpftime_amd_syscall_detach(detach);  // a perf link: its syscall attachment
+  if (udetach) bpftime_amd_uprobe_detach(udetach);  // ... or its bound uprobe attachment
 }
 
 void bpftime_amd_reset(void) {
@@ -156,6 +158,7 @@ void bpftime_amd_reset(void) {
   r.lpm_maps = 0;
   (void)detach;
   syscall_detach_all();  // the link-made attachments and the direct ones
+  uprobe_detach_all();
   if (r.d_maptab) hipMemset(r.d_maptab, 0, (sizeof(DMap) + sizeof(DPerf)) * kMaxFds);
   r.perf_dirty = false;  // (no perf record is left, and the table says so)
   r.arena_used = 0;

@@ -84,6 +84,11 @@ struct LinkRec {
   uint32_t prog_fd = 0, target = 0, attach_type = 0, flags = 0;
   bool perf = false;  // target is a perf event record (handles.cpp link_perf)
   int attach_id = 0;  // a perf link to a sys_enter / sys_exit tracepoint: its syscall attachment (syscall_dispatch.cpp)
+  // bpf_link_handler::attach_cookie (link_handler.hpp:20): what
+  // bpf_get_attach_cookie answers while the program runs for this link
+  bool has_cookie = false;
+  uint64_t cookie = 0;
+  int uprobe_id = 0;  // a perf link to a uprobe event bound to a function: its attachment (uprobe_dispatch.cpp)
 };
 
 enum class HKind : uint8_t { NONE, MAP, PROG, LINK, PERF };
@@ -182,15 +187,29 @@ __attribute__((visibility("hidden"))) int alloc_fd(int fd);
 // What the syscall dispatch needs to know of a loaded VM's program
 // (vm_api.cpp): bit 0 it calls bpf_override_return / bpf_set_retval (58 /
 // 187), bit 1 it may store into the memory r1 points to (its unit: the
-// dispatch then runs it on a copy of the records).  -1: no program loaded.
-constexpr int kProgSetsRetval = 1, kProgStoresCtx = 2;
+// dispatch then runs it on a copy of the records), bit 2 it calls
+// bpf_get_stackid / bpf_get_stack (27 / 67).  -1: no program loaded.
+constexpr int kProgSetsRetval = 1, kProgStoresCtx = 2, kProgReadsStacks = 4;
 int vm_prog_flags(const ::ebpf_vm *vm);
 // Drops every syscall attachment (bpftime_amd_reset; syscall_dispatch.cpp).
 void syscall_detach_all();
+// The cookie of syscall attachment `id` (a cookie link's; handles.cpp): what
+// bpf_get_attach_cookie answers in its callbacks.  -1: no such attachment.
+int syscall_attach_set_cookie(int id, uint64_t cookie);
+// Drops every uprobe attachment (bpftime_amd_reset; uprobe_dispatch.cpp).
+void uprobe_detach_all();
 // A loaded program's map effects (loader.hpp FastForm::map_fx, the syscall /
 // raw entry form): per map fd FX_* bits and the bits that may reach any map.
 // -1: no program loaded.
 int vm_map_effects(const ::ebpf_vm *vm, std::map<int32_t, uint8_t> &fx, uint8_t &any);
+// The commute analysis of the dispatches (syscall_dispatch.cpp): whether two
+// of the loaded programs may not commute -- both reach one map and one writes
+// it (a store, a fetching / non-add atomic, update / delete / ring calls) or
+// adds to it while the other reads it; counter adds commute with counter adds,
+// reads with reads; effects the loader cannot place reach every map.  1 with
+// the first such pair and the map's fd (-1: unplaced effects) in the non-null
+// outs, 0 none, -1 a program is not loaded.
+int first_map_conflict(const std::vector<const ::ebpf_vm *> &vms, size_t *first, size_t *second, int *map);
 // Whether a loaded program may reach a QUEUE / STACK map (loader.cpp
 // qs_call_sites): such a program does not commute with itself across
 // records, so the syscall dispatch runs it only in ORDERED dispatches.

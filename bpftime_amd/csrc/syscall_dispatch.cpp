@@ -140,31 +140,9 @@ std::vector<Attach> ordered_attachments() {
 // counter adds; reads with reads.  Programs whose accesses the loader cannot
 // place reach every map.  -1 when a program is not loaded.
 int conflicts(const std::vector<Attach> &order) {
-  using bpftime_amd::FX_ADD;
-  using bpftime_amd::FX_READ;
-  using bpftime_amd::FX_WRITE;
-  struct Fx {
-    std::map<int32_t, uint8_t> m;
-    uint8_t any;
-  };
-  std::vector<Fx> fx(order.size());
-  for (size_t i = 0; i < order.size(); i++)
-    if (bpftime_amd::vm_map_effects(order[i].vm.get(), fx[i].m, fx[i].any) < 0) return -1;
-  auto clash = [](uint8_t a, uint8_t b) {
-    return ((a & FX_WRITE) && b) || ((b & FX_WRITE) && a) || ((a & FX_ADD) && (b & FX_READ)) ||
-           ((b & FX_ADD) && (a & FX_READ));
-  };
-  for (size_t i = 0; i < fx.size(); i++)
-    for (size_t j = i + 1; j < fx.size(); j++) {
-      if (clash(fx[i].any, fx[j].any)) return 1;
-      for (const auto &kv : fx[i].m) {
-        auto it = fx[j].m.find(kv.first);
-        if (clash(kv.second | fx[i].any, (it == fx[j].m.end() ? 0 : it->second) | fx[j].any)) return 1;
-      }
-      for (const auto &kv : fx[j].m)
-        if (clash(kv.second | fx[j].any, fx[i].any)) return 1;
-    }
-  return 0;
+  std::vector<const struct ebpf_vm *> vms;
+  for (const Attach &a : order) vms.push_back(a.vm.get());
+  return bpftime_amd::first_map_conflict(vms, nullptr, nullptr, nullptr);
 }
 
 // 1 thread-ordered, 0 program-major, -1 error
@@ -318,6 +296,50 @@ int64_t dispatch(const Records &r, int64_t *out_rets, uint32_t flags, void *stre
 }
 
 }  // namespace
+
+// (runtime.hpp: the analysis above, shared with the uprobe dispatch, which
+// names the pair it refuses)
+int bpftime_amd::first_map_conflict(const std::vector<const struct ebpf_vm *> &vms, size_t *first, size_t *second,
+                                    int *map) {
+  struct Fx {
+    std::map<int32_t, uint8_t> m;
+    uint8_t any;
+  };
+  std::vector<Fx> fx(vms.size());
+  for (size_t i = 0; i < vms.size(); i++)
+    if (vm_map_effects(vms[i], fx[i].m, fx[i].any) < 0) return -1;
+  auto clash = [](uint8_t a, uint8_t b) {
+    return ((a & FX_WRITE) && b) || ((b & FX_WRITE) && a) || ((a & FX_ADD) && (b & FX_READ)) ||
+           ((b & FX_ADD) && (a & FX_READ));
+  };
+  for (size_t i = 0; i < fx.size(); i++)
+    for (size_t j = i + 1; j < fx.size(); j++) {
+      int hit = -2;  // -1: effects the loader could not place on a map
+      if (clash(fx[i].any, fx[j].any)) hit = -1;
+      for (const auto &kv : fx[i].m) {
+        if (hit != -2) break;
+        auto it = fx[j].m.find(kv.first);
+        if (clash(kv.second | fx[i].any, (it == fx[j].m.end() ? 0 : it->second) | fx[j].any)) hit = kv.first;
+      }
+      for (const auto &kv : fx[j].m) {
+        if (hit != -2) break;
+        if (clash(kv.second | fx[j].any, fx[i].any)) hit = kv.first;
+      }
+      if (hit == -2) continue;
+      if (first) *first = i;
+      if (second) *second = j;
+      if (map) *map = hit;
+      return 1;
+    }
+  return 0;
+}
+
+int bpftime_amd::syscall_attach_set_cookie(int id, uint64_t cookie) {
+  std::lock_guard<std::mutex> g(g_mu);
+  for (const Attach &a : g_attach)
+    if (a.id == id) return bpftime_amd_vm_set_attach(a.vm.get(), 0, cookie);  // (a tracepoint probes no function)
+  return -1;
+}
 
 void bpftime_amd::syscall_detach_all() {
   std::lock_guard<std::mutex> g(g_mu);

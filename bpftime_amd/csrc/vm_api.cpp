@@ -478,6 +478,10 @@ class Mi355xVm {
   uint64_t task_uid_gid = 0;
   char task_comm[64] = {};
   std::mutex task_mu;
+  // the attachment this VM runs for (bpf_get_func_ip / bpf_get_attach_cookie):
+  // bpftime_amd_vm_set_attach; both 0 by default (guarded by task_mu)
+  uint64_t attach_func_ip = 0;
+  uint64_t attach_cookie = 0;
 
   bool loaded = false;
   std::mutex img_mu;                 // guards img (replaced by tail-call relinks)
@@ -525,6 +529,11 @@ class Mi355xVm {
       const char *base = strrchr(exe, '/');
       strncpy(task_comm, base ? base + 1 : exe, sizeof(task_comm) - 1);
     }
+  }
+  void attach_into(uint64_t &func_ip, uint64_t &cookie) {
+    std::lock_guard<std::mutex> g(task_mu);
+    func_ip = attach_func_ip;
+    cookie = attach_cookie;
   }
   void task_into(uint64_t &uid_gid, uint64_t comm[8]) {
     std::lock_guard<std::mutex> g(task_mu);
@@ -779,16 +788,27 @@ int Mi355xVm::exec_batch(const ebpf_batch *b) {
     error = "no program loaded";
     return -1;
   }
-  if (!b || b->ctx_kind > EBPF_CTX_SYSCALL_EXIT || (b->count && !b->data) || (b->count && !b->stride && !b->descs)) {
+  if (!b || b->ctx_kind > EBPF_CTX_UPROBE || (b->count && !b->data) || (b->count && !b->stride && !b->descs)) {
     error = "invalid batch";
+    return -1;
+  }
+  // the uprobe ctx runs on the raw kernel: the unit is a pt_regs (r2 = 168),
+  // and the recorded caller / clock and the override state apply as they do
+  // to the syscall kinds (EBPF_CTX_UPROBE, include/ebpf-vm.h)
+  const bool uprobe = b->ctx_kind == EBPF_CTX_UPROBE;
+  if (uprobe && (b->descs || (b->count && (b->stride < kPtRegsBytes || b->stride % 8 != 0 ||
+                                            (uintptr_t)b->data % 8 != 0)))) {
+    error = "an uprobe batch needs 8-aligned units of at least " + std::to_string(kPtRegsBytes) +
+            " bytes (struct pt_regs) at a stride that is a multiple of 8, and no descriptors";
     return -1;
   }
   // the sys_exit ctx runs on the syscall kernel: only r2 (the ctx size) and
   // the window differ (EBPF_CTX_SYSCALL_EXIT, include/ebpf-vm.h)
   const bool sys_exit = b->ctx_kind == EBPF_CTX_SYSCALL_EXIT;
-  const uint32_t kind = sys_exit ? CTX_SYSCALL : b->ctx_kind;
-  if (b->sys_state && (kind != CTX_SYSCALL || (b->sys_phase != 1 && b->sys_phase != 2))) {
-    error = "sys_state needs a syscall batch with sys_phase 1 (enter) or 2 (exit)";
+  const uint32_t kind = sys_exit ? CTX_SYSCALL : uprobe ? CTX_RAW : b->ctx_kind;
+  if (b->sys_state && ((kind != CTX_SYSCALL && !uprobe) || (b->sys_phase != 1 && b->sys_phase != 2))) {
+    error = uprobe ? "sys_state needs sys_phase 1 (enter) or 2 (exit)"
+                   : "sys_state needs a syscall batch with sys_phase 1 (enter) or 2 (exit)";
     return -1;
   }
   if (b->descs && (kind == CTX_SYSCALL || !b->umem_bytes)) {
@@ -811,8 +831,8 @@ int Mi355xVm::exec_batch(const ebpf_batch *b) {
                        R{"ktime", b->ktime_off, b->ktime_arr, b->ktime_stride}}) {
       if (!o.off && !o.arr) continue;
       std::string bad;
-      if (kind != CTX_SYSCALL || b->descs)
-        bad = "a syscall batch only";
+      if ((kind != CTX_SYSCALL && !uprobe) || b->descs)
+        bad = uprobe ? "not with descriptors" : "a syscall batch only";
       else if (o.off && o.arr)
         bad = "an offset or an array, not both";
       else if (o.off && (o.off < 0 || o.off % 8 != 0 || (uint64_t)o.off + 8 > extent))
@@ -898,7 +918,7 @@ int Mi355xVm::exec_batch(const ebpf_batch *b) {
   }
   p.maps = r.d_maptab;
   p.data = (uint8_t *)b->data;
-  p.lens = kind == CTX_SYSCALL ? nullptr : b->lens;
+  p.lens = kind == CTX_SYSCALL || uprobe ? nullptr : b->lens;
   p.verdicts = b->verdicts;
   p.rets = b->rets;
   p.out_data_off = b->data_off_out;
@@ -940,13 +960,15 @@ int Mi355xVm::exec_batch(const ebpf_batch *b) {
                         b->stack_fixed_depth, b->stack_max_depth};
   p.pid_tgid = ((uint64_t)(uint32_t)getpid() << 32) | (uint32_t)syscall(SYS_gettid);
   task_into(p.task_uid_gid, p.task_comm);
+  attach_into(p.attach_func_ip, p.attach_cookie);
   p.trace_log = trace_log().d;  // (made at load when the program calls helper 6)
   p.trace_cap = trace_log().cap;
   p.arena_lo = (uint64_t)(uintptr_t)r.arena;
   p.arena_hi = p.arena_lo + r.arena_size;
   p.step_limit = step_limit;
   // (syscall kinds: r2 = sizeof the ctx, syscall_trace_attach_impl.cpp:46)
-  p.fixed_len = kind != CTX_SYSCALL ? b->fixed_len : sys_exit ? 24 : 64;
+  // (uprobe: sizeof(struct pt_regs), frida_attach_entry.hpp:54-55)
+  p.fixed_len = uprobe ? kPtRegsBytes : kind != CTX_SYSCALL ? b->fixed_len : sys_exit ? 24 : 64;
   p.stack_size = prog.stack_size;
   p.stack_stride = lane_stride(prog.stack_size);
   p.ctx_stride = lane_stride(kXdpCtxBytes);
@@ -1518,7 +1540,8 @@ int vm_prog_flags(const ::ebpf_vm *vm) {
   if (!vm || !vm->impl->loaded) return -1;
   auto im = vm->impl->image();
   if (!im) return -1;
-  return (im->prog.sets_retval ? kProgSetsRetval : 0) | (im->fr.stores_unit ? kProgStoresCtx : 0);
+  return (im->prog.sets_retval ? kProgSetsRetval : 0) | (im->fr.stores_unit ? kProgStoresCtx : 0) |
+         (im->prog.reads_stacks ? kProgReadsStacks : 0);
 }
 
 int vm_map_effects(const ::ebpf_vm *vm, std::map<int32_t, uint8_t> &fx, uint8_t &any) {
@@ -1608,6 +1631,10 @@ int64_t seq_dispatch(const std::vector<SeqAttach> &progs, const SysLayout &lay, 
         p.tasks[ntasks++] = tk;
       }
       q.task = ti;
+    }
+    {  // its attach cookie (a link's; a syscall tracepoint has no func_ip)
+      uint64_t ip;
+      vm->attach_into(ip, p.cookies[p.nprogs - 1]);
     }
     may_delete |= im->prog.may_delete;
     names_lpm |= im->fr.names_lpm;
@@ -1798,7 +1825,7 @@ int ebpf_exec_batch(const struct ebpf_vm *vm, const struct ebpf_batch *batch) {
 }
 
 int ebpf_set_ctx_kind(struct ebpf_vm *vm, uint32_t ctx_kind) {
-  if (ctx_kind > EBPF_CTX_SYSCALL_EXIT) return -1;
+  if (ctx_kind > EBPF_CTX_UPROBE) return -1;
   vm->impl->ctx_kind = ctx_kind;
   return 0;
 }
@@ -1823,7 +1850,8 @@ int bpftime_amd_register_default_helpers(struct ebpf_vm *vm) {
            {15, "bpf_get_current_uid_gid"},  {16, "bpf_get_current_comm"},
            {36, "bpf_probe_write_user"},     {125, "bpf_ktime_get_boot_ns"},
            {160, "bpf_ktime_get_coarse_ns"}, {25, "bpf_perf_event_output"},
-           {27, "bpf_get_stackid"},          {67, "bpf_get_stack"}};
+           {27, "bpf_get_stackid"},          {67, "bpf_get_stack"},
+           {173, "bpf_get_func_ip"},         {174, "bpf_get_attach_cookie"}};
   int err = 0;
   for (auto &e : h) err |= ebpf_register(vm, e.id, e.name, nullptr);
   // ... and bpf_trace_printk once the host enabled it (bpftime_amd_enable_trace_printk)
@@ -1907,6 +1935,14 @@ int bpftime_amd_vm_set_task(struct ebpf_vm *vm, const char *comm, const uint64_t
     strncpy(vm->impl->task_comm, comm, 63);
   }
   if (uid_gid) vm->impl->task_uid_gid = *uid_gid;
+  return 0;
+}
+
+int bpftime_amd_vm_set_attach(struct ebpf_vm *vm, uint64_t func_ip, uint64_t cookie) {
+  if (!vm) return -1;
+  std::lock_guard<std::mutex> g(vm->impl->task_mu);
+  vm->impl->attach_func_ip = func_ip;
+  vm->impl->attach_cookie = cookie;
   return 0;
 }
 

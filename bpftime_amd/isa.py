@@ -88,6 +88,8 @@ BPF_FUNC_ktime_get_coarse_ns = 160
 BPF_FUNC_perf_event_output = 25
 BPF_FUNC_get_stackid = 27
 BPF_FUNC_get_stack = 67
+BPF_FUNC_get_func_ip = 173
+BPF_FUNC_get_attach_cookie = 174
 
 # bpf_get_stackid / bpf_get_stack flags (linux/bpf.h)
 BPF_F_SKIP_FIELD_MASK = 0xFF

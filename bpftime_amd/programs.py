@@ -20,7 +20,7 @@ import struct
 
 from .isa import (Asm, BPF_ANY, BPF_FUNC_get_current_pid_tgid, BPF_FUNC_ktime_get_ns, BPF_FUNC_map_lookup_elem,
                   BPF_FUNC_map_update_elem, BPF_FUNC_override_return, BPF_FUNC_set_retval,
-                  BPF_FUNC_ringbuf_output, BPF_FUNC_perf_event_output, BPF_FUNC_get_stackid, BPF_NOEXIST, ATOMIC_ADD, XDP_DROP, XDP_PASS, XDP_TX, XDP_ABORTED)
+                  BPF_FUNC_ringbuf_output, BPF_FUNC_perf_event_output, BPF_FUNC_get_stackid, BPF_FUNC_get_func_ip, BPF_FUNC_get_attach_cookie, BPF_NOEXIST, ATOMIC_ADD, XDP_DROP, XDP_PASS, XDP_TX, XDP_ABORTED)
 
 ETH_P_IP_LE = 0x0008  # htons(0x0800) as read by a little-endian ldxh
 IPPROTO_TCP, IPPROTO_UDP = 6, 17
@@ -939,4 +939,53 @@ def stack_count(stack_fd: int, counts_fd: int, flags: int = 1 << 8) -> bytes:
     a.jmp("jeq", 0, 0, "out")
     a.mov64(1, 1).atomic(8, ATOMIC_ADD, 0, 0, 1)
     a.label("out").mov64(0, "r6")
+    return a.exit().assemble()
+
+
+PT_REGS_PARM1_OFF, PT_REGS_RC_OFF, PT_REGS_IP_OFF = 112, 80, 128  # x86-64 struct pt_regs: di, ax, ip
+
+
+def _count_key_r0(a: Asm, map_fd: int) -> Asm:
+    """counts[r0] += 1 in a HASH of u64 -> u64, syscount's way: a key that is
+    not there is inserted as 0 (BPF_NOEXIST; losing that race to another unit
+    is fine) and looked up again, then the value takes an atomic add.  r0 = 0."""
+    a.stx(8, 10, -8, 0)
+    a.mov64(2, "r10").add64(2, -8).ld_map_fd(1, map_fd).call(BPF_FUNC_map_lookup_elem)
+    a.jmp("jne", 0, 0, "add")
+    a.st(8, 10, -16, 0)
+    a.mov64(2, "r10").add64(2, -8).mov64(3, "r10").add64(3, -16).mov64(4, BPF_NOEXIST)
+    a.ld_map_fd(1, map_fd).call(BPF_FUNC_map_update_elem)
+    a.mov64(2, "r10").add64(2, -8).ld_map_fd(1, map_fd).call(BPF_FUNC_map_lookup_elem)
+    a.jmp("jeq", 0, 0, "out")
+    a.label("add").mov64(1, 1).atomic(8, ATOMIC_ADD, 0, 0, 1)
+    a.label("out").mov64(0, 0)
+    return a.exit()
+
+
+def func_ip_count(map_fd: int) -> bytes:
+    """A uprobe that counts calls per probed function: counts[bpf_get_func_ip(ctx)]
+    += 1.  map_fd: HASH, u64 key, u64 value."""
+    a = Asm()
+    a.call(BPF_FUNC_get_func_ip)
+    return _count_key_r0(a, map_fd).assemble()
+
+
+def cookie_tag(map_fd: int) -> bytes:
+    """Counts runs per attachment: counts[bpf_get_attach_cookie(ctx)] += 1
+    (0 for an attachment without a cookie).  map_fd: HASH, u64 key, u64 value."""
+    a = Asm()
+    a.call(BPF_FUNC_get_attach_cookie)
+    return _count_key_r0(a, map_fd).assemble()
+
+
+def override_if_arg0(value: int, arg0: int = 0) -> bytes:
+    """An override program: ``bpf_override_return(ctx, value)`` when
+    PT_REGS_PARM1(ctx) == arg0.  Returns 0."""
+    a = Asm()
+    a.ldx(8, 2, 1, PT_REGS_PARM1_OFF)
+    a.lddw(3, arg0 & 0xFFFFFFFFFFFFFFFF)
+    a.jmp("jne", 2, "r3", "ret")
+    a.lddw(2, value & 0xFFFFFFFFFFFFFFFF)
+    a.call(BPF_FUNC_override_return)
+    a.label("ret").mov64(0, 0)
     return a.exit().assemble()

@@ -14,10 +14,12 @@ from typing import Optional
 import numpy as np
 
 from . import isa
-from ._lib import BpfLinkCreateArgs, BpfMapAttr, EbpfBatch, LaunchInfo, SysRecords, TraceLine, lib
+from ._lib import BpfLinkCreateArgs, BpfMapAttr, CallRecords, EbpfBatch, LaunchInfo, SysRecords, TraceLine, lib
 from ._lib import PerfEvent as PerfEventRec
 
-CTX_RAW, CTX_XDP, CTX_SYSCALL, CTX_SYSCALL_EXIT = 0, 1, 2, 3
+CTX_RAW, CTX_XDP, CTX_SYSCALL, CTX_SYSCALL_EXIT, CTX_UPROBE = 0, 1, 2, 3, 4
+UPROBE, URETPROBE, UPROBE_OVERRIDE, UREPLACE = 6, 7, 1008, 1009  # uprobe attach kinds (include/bpftime_amd.h)
+PT_REGS_BYTES = 168  # x86-64 struct pt_regs: the EBPF_CTX_UPROBE unit
 SYSCALL_RECORD, SYSCALL_RECORD_FULL, SYSCALL_RECORD_TIMED = 64, 96, 128  # include/bpftime_amd.h replay records
 DISPATCH_THREADS, DISPATCH_PROGRAMS = 0x100, 0x200  # dispatch plans (include/bpftime_amd.h)
 BATCH_SYNC, BATCH_ORDERED, BATCH_UNCHECKED, BATCH_SYS_NR, BATCH_TIMED = 0x1, 0x2, 0x4, 0x8, 0x10
@@ -443,6 +445,12 @@ class VM:
             raise EbpfError("get_task failed")
         return buf.raw.split(b"\0", 1)[0], u.value
 
+    def set_attach(self, func_ip: int = 0, cookie: int = 0) -> None:
+        """What bpf_get_func_ip / bpf_get_attach_cookie answer in this VM's
+        launches (bpftime_amd_vm_set_attach); both 0 by default."""
+        if lib().bpftime_amd_vm_set_attach(C.c_void_p(self.h), func_ip, cookie):
+            raise EbpfError("set_attach failed")
+
     def last_batch_ms(self) -> float:
         """Kernel time of this VM's last BATCH_TIMED batch (ms; -1 none)."""
         return lib().bpftime_amd_last_batch_ms(self.h)
@@ -456,7 +464,8 @@ class VM:
                    sys_nr: Optional[int] = None, pid_tgid_off: int = 0, ktime_off: int = 0,
                    stacks: Optional[DeviceBuffer] = None, stack_unit_stride: int = 0, stack_frame_stride: int = 0,
                    stack_depths: Optional[DeviceBuffer] = None, stack_fixed_depth: int = 0,
-                   stack_max_depth: int = 0) -> int:
+                   stack_max_depth: int = 0, sys_state: Optional[DeviceBuffer] = None,
+                   sys_ret: Optional[DeviceBuffer] = None, sys_phase: int = 0) -> int:
         """descs: AF_XDP descriptor mode ({u64 addr; u32 len; u32 options} per
         unit, frames at data + addr inside umem_bytes; stride = chunk size).
         pid_tgid_off / ktime_off: the recorded caller / clock of a syscall
@@ -476,7 +485,9 @@ class VM:
                       ktime_off=ktime_off, stack_arr=stacks.ptr if stacks else None,
                       stack_unit_stride=stack_unit_stride, stack_frame_stride=stack_frame_stride,
                       stack_depths=stack_depths.ptr if stack_depths else None,
-                      stack_fixed_depth=stack_fixed_depth, stack_max_depth=stack_max_depth)
+                      stack_fixed_depth=stack_fixed_depth, stack_max_depth=stack_max_depth,
+                      sys_state=sys_state.ptr if sys_state else None, sys_ret=sys_ret.ptr if sys_ret else None,
+                      sys_phase=sys_phase)
         if sys_nr is not None:
             b.flags |= BATCH_SYS_NR
         rc = lib().ebpf_exec_batch(C.c_void_p(self.h), C.byref(b))
@@ -529,9 +540,57 @@ def prog_create(code: bytes, name: str, prog_type: int, fd: int = -1) -> int:
     return r
 
 
-def link_create(prog_fd: int, target: int, attach_type: int, fd: int = -1) -> int:
+def link_create(prog_fd: int, target: int, attach_type: int, fd: int = -1, cookie: int = 0) -> int:
+    """cookie: perf_event.bpf_cookie, read for attach type 41 only."""
     a = BpfLinkCreateArgs(prog_fd=prog_fd, target_fd=target, attach_type=attach_type)
+    a.attach_union[0] = cookie
     return lib().bpftime_link_create(fd, C.byref(a))
+
+
+def uprobe_attach(prog_fd: int, func: int, kind: int = UPROBE, cookie: Optional[int] = None) -> int:
+    """A program at function address `func` of the recorded calls: UPROBE,
+    URETPROBE, UPROBE_OVERRIDE or UREPLACE; the attach id."""
+    c = C.c_uint64(cookie) if cookie is not None else None
+    i = lib().bpftime_amd_uprobe_attach(prog_fd, func, kind, C.byref(c) if c is not None else None)
+    if i < 0:
+        raise EbpfError(f"uprobe attach failed (errno {C.get_errno()}): {_err()}")
+    return i
+
+
+def uprobe_attach_link(link_fd: int, func: int) -> int:
+    """Binds a link to a uprobe perf event to the address its module:offset
+    resolved to; kind and cookie come from the records."""
+    i = lib().bpftime_amd_uprobe_attach_link(link_fd, func)
+    if i < 0:
+        raise EbpfError(f"uprobe attach failed (errno {C.get_errno()}): {_err()}")
+    return i
+
+
+def uprobe_detach(i: int) -> int:
+    return lib().bpftime_amd_uprobe_detach(i)
+
+
+def uprobe_dispatch(func: Optional[DeviceBuffer], n: int, enter: Optional[DeviceBuffer] = None,
+                    leave: Optional[DeviceBuffer] = None, pid_tgid: Optional[DeviceBuffer] = None,
+                    clock: Optional[DeviceBuffer] = None, out_state: Optional[DeviceBuffer] = None,
+                    out_rets: Optional[DeviceBuffer] = None, flags: int = BATCH_SYNC, stream: int = 0,
+                    stacks: Optional[DeviceBuffer] = None, stack_unit_stride: int = 0, stack_frame_stride: int = 0,
+                    stack_depths: Optional[DeviceBuffer] = None, stack_fixed_depth: int = 0,
+                    stack_max_depth: int = 0) -> int:
+    """Runs the uprobe attachments over n recorded calls (struct
+    bpftime_amd_call_records): func (u64 per call), enter / leave (168-B
+    pt_regs per call), pid_tgid (u64), clock (2 x u64), the stacks as
+    exec_batch's; out_state (u32) / out_rets (i64) receive the overrides.
+    Returns the failed callbacks (BATCH_SYNC)."""
+    p = lambda b: b.ptr if b else None  # noqa: E731
+    r = CallRecords(enter=p(enter), leave=p(leave), func=p(func), pid_tgid=p(pid_tgid), clock=p(clock),
+                    stack_arr=p(stacks), stack_unit_stride=stack_unit_stride,
+                    stack_frame_stride=stack_frame_stride, stack_depths=p(stack_depths),
+                    stack_fixed_depth=stack_fixed_depth, stack_max_depth=stack_max_depth, count=n)
+    rc = lib().bpftime_amd_uprobe_dispatch(C.byref(r), p(out_state), p(out_rets), flags, stream or None)
+    if rc < 0:
+        raise EbpfError(f"uprobe dispatch failed: {_err()}")
+    return rc
 
 
 def syscall_attach(prog_fd: int, sys_nr: int, enter: bool = True) -> int:

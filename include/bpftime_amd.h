@@ -43,7 +43,7 @@ struct bpf_link_create_args {
 	uint32_t target_fd;      /* union { target_fd; target_ifindex; } */
 	uint32_t attach_type;    /* BPF_XDP = 37 (runtime/include/bpftime_epoll.h:1158) */
 	uint32_t flags;
-	uint64_t attach_union[4];
+	uint64_t attach_union[4]; /* attach_type 41: [0] = perf_event.bpf_cookie (link_handler.hpp:25-31) */
 };
 
 #define BPFTIME_AMD_BPF_XDP 37
@@ -217,6 +217,14 @@ int bpftime_amd_perf_event_ring_state(int perf_fd, uint64_t *head, uint64_t *tai
  * tracepoint id does not resolve, -1 when the device cannot load the
  * program. */
 int bpftime_attach_perf_to_bpf(int perf_fd, int bpf_fd);
+/* bpftime_shm.cpp:255-260: the same link with an attach cookie, what
+ * bpf_get_attach_cookie (174) answers while the linked program runs for this
+ * link (bpf_attach_ctx.cpp:380-388 sets it around every callback, syscall
+ * tracepoints included).  A link made without one answers 0; so does
+ * bpftime_link_create with an attach type other than 41, whose attach_union
+ * holds no perf_event.bpf_cookie (link_handler.hpp:25-31), while a type-41
+ * link always carries attach_union[0], 0 included.  Same errors as above. */
+int bpftime_attach_perf_to_bpf_with_cookie(int perf_fd, int bpf_fd, uint64_t cookie);
 /* The same link at `fd` (-1: a fresh one), leaving a link to an unresolvable
  * tracepoint id as a record (the JSON import's add_bpf_link: the reference
  * resolves the id only when its agent attaches). */
@@ -403,6 +411,13 @@ int64_t bpftime_amd_ringbuf_fetch(int fd, void *out, uint64_t cap, uint64_t *use
  * it is.  The getter copies 64 bytes of comm (zero from its NUL on). */
 int bpftime_amd_vm_set_task(struct ebpf_vm *vm, const char *comm, const uint64_t *uid_gid);
 int bpftime_amd_vm_get_task(const struct ebpf_vm *vm, char *comm, uint64_t *uid_gid);
+/* What bpf_get_func_ip (173) and bpf_get_attach_cookie (174) answer in this
+ * VM's launches (bpf_helper.cpp:684-700): the probed function's address and
+ * the attachment's cookie.  Both 0 until set: the reference answers 0 outside
+ * any attach callback and for an attachment without a cookie.  The dispatches
+ * set them per attachment (bpftime_amd_uprobe_dispatch; a cookie link in
+ * bpftime_amd_syscall_dispatch*, where 173 answers 0). */
+int bpftime_amd_vm_set_attach(struct ebpf_vm *vm, uint64_t func_ip, uint64_t cookie);
 
 /* bpf_trace_printk (6) is off until the host enables it here (and off again
  * after bpftime_amd_reset): while off it is no default helper
@@ -523,6 +538,95 @@ struct bpftime_amd_sys_records {
 };
 int64_t bpftime_amd_syscall_dispatch_soa(const struct bpftime_amd_sys_records *records, int64_t *out_rets,
                                          uint32_t flags, void *stream);
+
+/* ---- uprobe replay (Uprobe replay) ----
+ * The reference's third attach family (attach/frida_uprobe_attach_impl):
+ * programs attached to a function's entry (uprobe, 6), its return (uretprobe,
+ * 7), or in place of it (override 1008, replace 1009).  Here the calls are
+ * recorded and replayed: per call the x86-64 struct pt_regs (21 u64, 168 B:
+ * di at +112, ax at +80, ip at +128) at entry and at return, the called
+ * function's address, and optionally the caller, the clocks and the caller's
+ * stack.
+ *
+ * Which attachments run at a function:
+ *  - a function whose first attachment is an override / replace runs only
+ *    that one, on the entry registers, and every later attach there fails
+ *    with -1 + EEXIST (frida_uprobe_attach_impl.cpp:64-79);
+ *  - otherwise its uprobes run at entry and its uretprobes at return, each in
+ *    attach order (frida_internal_attach_entry.cpp:221-239); an override /
+ *    replace attached after them is kept and never runs, the function being
+ *    hooked as a listener (:128-165).
+ * bpf_get_func_ip answers `func` inside a uprobe / uretprobe and 0 inside an
+ * override / replace (frida_attach_entry.hpp:25-40); bpf_get_attach_cookie
+ * the attachment's cookie or 0.  Each program runs on a copy of the record
+ * (the reference hands the callback a local pt_regs): stores through r1 never
+ * reach `enter` / `leave`.
+ *
+ * _attach: kind 6 / 7 / 1008 / 1009; `cookie` NULL: none.  An attach id, or -1
+ * (EINVAL: not a program / a bad kind / the device cannot load it; EEXIST).
+ * _attach_link binds a link record whose target is a uprobe perf event (type
+ * 6 / 7 / 1008) to the address its module:offset resolved to in the recording;
+ * kind and cookie come from the records.  bpftime_amd_link_attached stays 0
+ * for such a link (it drives no syscall attachment); _uprobe_link_bound tells
+ * 1 bound / 0 not / -1 no link.  _detach: 0, or -1 + ENOENT. */
+#define BPFTIME_AMD_UPROBE 6
+#define BPFTIME_AMD_URETPROBE 7
+#define BPFTIME_AMD_UPROBE_OVERRIDE 1008
+#define BPFTIME_AMD_UREPLACE 1009
+#define BPFTIME_AMD_PT_REGS_BYTES 168
+int bpftime_amd_uprobe_attach(int prog_fd, uint64_t func, int kind, const uint64_t *cookie);
+int bpftime_amd_uprobe_attach_link(int link_fd, uint64_t func);
+int bpftime_amd_uprobe_link_bound(int link_fd);
+int bpftime_amd_uprobe_detach(int id);
+/* The recorded calls: device arrays, one entry per call.  stack_* as
+ * ebpf_batch's fields of the same names (include/ebpf-vm.h), indexed by the
+ * record. */
+struct bpftime_amd_call_records {
+  const void *enter;        /* count x 168 B pt_regs at entry, or NULL */
+  const void *leave;        /* count x 168 B pt_regs at return, or NULL */
+  const uint64_t *func;     /* count: the called function's address */
+  const uint64_t *pid_tgid; /* or NULL: the dispatching thread's */
+  const void *clock;        /* count x 16 B {ns at entry, ns at return}, or NULL: the device clock */
+  const void *stack_arr;
+  uint64_t stack_unit_stride, stack_frame_stride;
+  const uint32_t *stack_depths;
+  uint32_t stack_fixed_depth, stack_max_depth;
+  uint64_t count;
+};
+/* Runs every attachment over the records, program-major: the entry
+ * attachments in attach order, then the return attachments.  Per attachment
+ * the records of its function are gathered, in record order, into compact
+ * 192-B rows {pt_regs, pid_tgid, the phase's clock, record index} and the
+ * program runs over them as an EBPF_CTX_UPROBE batch; an attachment that
+ * matches no record launches nothing.  An override's bpf_override_return (58)
+ * / bpf_set_retval (187) sets bit 0 of out_state[i] and stores the value in
+ * out_rets[i]; a replace always does, with the program's r0; every other
+ * entry of both arrays keeps what the caller put there.  58 / 187 from a
+ * uprobe / uretprobe fail the unit.
+ * Program-major order equals the reference's per-call order when the attached
+ * programs commute (the syscall dispatch's analysis): two attachments that
+ * may not are refused before any launch, the error naming both programs and
+ * the map.  A dispatch with a single attachment takes EBPF_BATCH_ORDERED and
+ * gives the serial result.  Flags: EBPF_BATCH_SYNC / _ORDERED / _UNCHECKED /
+ * _TIMED.
+ * The call is never fully asynchronous: per attachment the host waits on the
+ * stream once, to read how many records matched (it sizes the rows and the
+ * batch from that count, and launches nothing for 0).  Without EBPF_BATCH_SYNC
+ * only the last attachment's batch and scatter are left in flight.
+ * A replace whose program fails its unit stores 0 and sets bit 0 (a failed
+ * exec reports r0 = 0) and is counted; the reference leaves that call's
+ * return alone (frida_uprobe_attach_impl.cpp:244-252).
+ * Returns the failed callbacks with EBPF_BATCH_SYNC, else 0; -1 with a named
+ * error (bpftime_amd_last_error) before any launch for: no records / `func`
+ * NULL, an entry attachment without `enter`, a return attachment without
+ * `leave`, stack fields that break ebpf_batch's rules, an override / replace
+ * attachment without out_state / out_rets. */
+int64_t bpftime_amd_uprobe_dispatch(const struct bpftime_amd_call_records *r, uint32_t *out_state,
+                                    int64_t *out_rets, uint32_t flags, void *stream);
+/* The last EBPF_BATCH_TIMED dispatch, summed over its attachments: the time of
+ * the count + scan launches, of the gather launches (ms, stream events), and
+ * the rows gathered.  Any out pointer may be NULL. */
+int bpftime_amd_uprobe_last_ms(float *count_ms, float *gather_ms, uint64_t *rows);
 
 /* ---- attach plugins (attach/base_attach_impl/base_attach_impl.hpp:24-71,
  * attach/simple_attach_impl/simple_attach_impl.cpp:7-55; csrc/attach.cpp) ----

@@ -59,7 +59,8 @@ void ebpf_set_error_print(struct ebpf_vm *vm, int (*error_printf)(FILE *stream, 
  * (probe_read_str / _user_str / _kernel_str), 58 (override_return), 65
  * (xdp_adjust_tail), 67 (get_stack, over the same stacks), 87-89 (map push / pop / peek), 125 / 160
  * (ktime_get_boot_ns / _coarse_ns), 130-133 (ringbuf output / reserve / submit /
- * discard), 182 (strncmp), 187 (set_retval) and 189 (xdp_load_bytes)
+ * discard), 173 (get_func_ip) / 174 (get_attach_cookie) (the running attachment's:
+ * bpftime_amd_vm_set_attach), 182 (strncmp), 187 (set_retval) and 189 (xdp_load_bytes)
  * (loader.cpp device_helper_supported).  0 / -1. */
 int ebpf_register(struct ebpf_vm *vm, unsigned int index, const char *name, void *fn);
 /* ebpf-vm.h:137: copy, patch (compat_ubpf.cpp:61-200), validate, pre-decode
@@ -95,6 +96,14 @@ ebpf_jit_fn ebpf_load_aot_object(struct ebpf_vm *vm, const void *buf, size_t buf
  * struct-of-arrays exit record {ctx, pid_tgid} (stride 32), or any record with that
  * layout at `stride`. */
 #define EBPF_CTX_SYSCALL_EXIT 3
+/* r1 = the unit, an x86-64 struct pt_regs (21 u64: di +112, ax +80, ip +128;
+ * frida_register_conversion.cpp:6-26), r2 = 168 (frida_attach_entry.hpp:54-55).
+ * Runs as EBPF_CTX_RAW does (lens / fixed_len unused; 8-aligned units at a
+ * stride >= 168 that is a multiple of 8, no descriptors) and, unlike it,
+ * honours pid_tgid_off / _arr, ktime_off / _arr and sys_state / sys_ret /
+ * sys_phase under the syscall kinds' rules.  bpftime_amd_uprobe_dispatch builds
+ * such batches. */
+#define EBPF_CTX_UPROBE 4
 
 #define EBPF_BATCH_SYNC 0x1    /* wait for completion; return the failed-unit count */
 /* one lane, units in index order (exact sequential semantics).  The only batches that run a
@@ -180,7 +189,8 @@ struct ebpf_batch {
 	 * and stack_max_depth in 1..127, and every STACK_TRACE map the program names
 	 * must hold stack_max_depth frames (value_size / 8); else the batch fails
 	 * (-1, named).  bpftime_amd_syscall_dispatch_records / _soa pass no stacks:
-	 * the helpers answer -ENOTSUP there. */
+	 * the helpers answer -ENOTSUP there; bpftime_amd_uprobe_dispatch passes the
+	 * recorded calls' stacks. */
 	const void *stack_arr;
 	uint64_t stack_unit_stride;
 	uint64_t stack_frame_stride;
