@@ -585,6 +585,64 @@ struct SeqParams {
 };
 static_assert(sizeof(SeqParams) <= 4096, "kernel arguments");
 
+// Thread-ordered uprobe replay (interp.hip k_up_seq, uprobe_dispatch.cpp): one
+// lane per recorded thread walks that thread's calls in record order and, per
+// call, runs the entry callbacks of the call's function in attach order, then
+// its return callbacks (attach/frida_uprobe_attach_impl: frida_internal_attach_
+// entry.cpp:221-239 on the calling thread).  The programs are the ones
+// uprobe_dispatch.cpp's running() yields: entry attachments, then return ones.
+constexpr uint8_t kUpPlain = 0, kUpOverride = 1, kUpReplace = 2;
+struct UpSeqProg {
+  const DInsn *prog;
+  const FInsn *fast;    // its ORDERED link (every counter add reaches memory at once)
+  uint64_t func;        // the function it is attached to
+  uint64_t cookie;      // bpf_get_attach_cookie (0: none)
+  uint8_t phase;        // 0: runs on the entry registers, 1: on the return registers
+  // kUpPlain (uprobe / uretprobe), kUpOverride, kUpReplace.  bpf_get_func_ip
+  // follows from it -- `func` inside a plain probe, 0 inside the other two
+  // (frida_attach_entry.hpp:25-40) -- and is not stored: 48-B entries would
+  // not fit the kernel arguments beside the identities
+  uint8_t kind;
+  uint16_t task;        // its VM's identity: UpSeqParams::tasks[task]
+  uint32_t pad;
+};
+static_assert(sizeof(UpSeqProg) == 40, "UpSeqProg is read with scalar loads");
+// One wave per block: the wave stages its 64 current records together between
+// barriers, and waves of one block would leave their ragged walks at different
+// records (Uprobe replay)
+constexpr uint32_t kUpSeqBlock = 64;
+struct UpSeqParams {
+  uint32_t nprogs;
+  uint32_t exact;         // one lane over every record (EBPF_BATCH_ORDERED)
+  uint64_t n;
+  // the records (include/bpftime_amd.h bpftime_amd_call_records), by index:
+  const uint64_t *enter;  // n x 21 u64 (null: no entry program runs)
+  const uint64_t *leave;  // n x 21 u64 (null: no return program runs)
+  const uint64_t *func;   // n
+  const uint64_t *pid;    // n, or null: pid_tgid below
+  const uint64_t *clock;  // n x {entry ns, return ns}, or null: the device clock
+  // thread t's records: perm[seg[t] .. seg[t + 1]) (record indexes in record
+  // order); null perm: the identity; null seg: one thread over [0, n)
+  const uint32_t *perm;
+  const uint32_t *seg;
+  uint64_t nseg;
+  uint32_t *out_state;    // override / replace: bit 0 of record i's word (nullable without such programs)
+  int64_t *out_rets;      // ... and the value
+  const DMap *maps;
+  uint32_t ncpu;
+  uint32_t checked;
+  uint64_t arena_lo, arena_hi;
+  uint64_t step_limit;
+  uint64_t lru_seq;
+  uint64_t pid_tgid;      // records without callers: the dispatching thread's
+  uint32_t *err_count;    // failed callbacks
+  uint8_t *trace_log;     // bpf_trace_printk's record log (trace_fmt.hpp), or null
+  uint64_t trace_cap;
+  UpSeqProg progs[kSeqMaxProgs];  // in the kernel arguments: scalar loads, no upload
+  SeqTask tasks[kSeqMaxTasks];
+};
+static_assert(sizeof(UpSeqParams) <= 4096, "kernel arguments");
+
 // Combining-table misses.  A deferred counter add that finds no table entry
 // (the set is full of other granules) does not become a memory-side atomic
 // at once: its lane appends {tag, delta} records (tag = address | (4-byte ?

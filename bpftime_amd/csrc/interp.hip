@@ -1753,6 +1753,214 @@ extern "C" int bpftime_amd_seq_prof(unsigned long long *out, int reset) {
 }
 #endif
 
+// Thread-ordered uprobe replay (common.hpp UpSeqParams; the host side is
+// uprobe_dispatch.cpp / vm_api.cpp useq_dispatch).  The reference runs a
+// call's callbacks on the calling thread (frida_internal_attach_entry.cpp:
+// 221-239: the function's uprobes at entry, its uretprobes at return, in
+// attach order; the override handler :243-277; a replace returns r0,
+// frida_uprobe_attach_impl.cpp:236-263): here lane t walks thread t's calls
+// in record order and, per call, runs the entry callbacks of the call's
+// function and then its return callbacks, each on a fresh copy of the phase's
+// pt_regs.  A block is one wave (common.hpp kUpSeqBlock).  Per phase the wave
+// stages its 64 current records together: lane l moves words l, l + 64, ... of
+// the 64 x 21-word image, so a wave load covers 512 contiguous image bytes
+// made of whole runs of one record's consecutive words (a lane-per-record copy
+// would put neighbouring lanes 168 B apart); each callback then copies its
+// lane's 21 words from the image inside LDS.  The callbacks run in the C++
+// tier (run_loop, private 512-B stacks) with the ORDERED links, as k_sys_seq's
+// C++ tier does; there is no asm tier here.
+__global__ __launch_bounds__(kUpSeqBlock) void k_up_seq(UpSeqParams p) {
+  constexpr uint32_t kW = kPtRegsBytes / 8;
+  // r0..r10 columns and the dummy slot, at run_loop's column stride (kBlock)
+  __shared__ uint64_t Rf[11 * kBlock + kUpSeqBlock];
+  __shared__ uint64_t img[kW * kUpSeqBlock];  // the staged records of the phase: [lane][21]
+  __shared__ uint64_t cx[kW * kUpSeqBlock];   // the running callback's ctx copy: [lane][21]
+  __shared__ uint64_t srec[kUpSeqBlock];      // the lanes' record indexes for the staging (all ones: none)
+  const uint32_t tid = threadIdx.x;
+  const uint64_t t = (uint64_t)blockIdx.x * kUpSeqBlock + tid;
+  uint64_t stk[kStackSize / 8];
+  const uint64_t stack_top = (uint64_t)(uintptr_t)(stk + kStackSize / 8);
+  uint64_t *const ctx = &cx[kW * tid];
+  Ctx c;
+  c.R = &Rf[tid];
+  // the programs see their ctx copy (LDS), their stack and the map arena
+  c.win = Win{0, 0, p.arena_lo, p.arena_hi, 0, 0, p.checked != 0};
+  c.dummy = (uint64_t)(uintptr_t)&Rf[11 * kBlock + tid];
+  c.verdicts = nullptr;
+  c.rets = nullptr;
+  c.step_limit = p.step_limit > 0xffffffffull ? 0xffffffffu : (uint32_t)p.step_limit;
+  c.c0a = c.c0d = c.c1a = c.c1d = 0;
+  c.c0s = c.c1s = 0;
+  uint64_t k = 0, end = 0;
+  if (t < p.nseg) {
+    k = p.seg ? p.seg[t] : 0;
+    end = p.seg ? p.seg[t + 1] : p.n;
+  }
+  const uint32_t nprogs = __builtin_amdgcn_readfirstlane(p.nprogs);
+  auto rfl64 = [](uint64_t v) {
+    return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v) |
+           ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)) << 32);
+  };
+  // the return-phase programs, as bits of a program mask (kSeqMaxProgs = 64)
+  uint64_t ret_mask = 0;
+  for (uint32_t a = 0; a < nprogs; a++)
+    ret_mask |= (uint64_t)(__builtin_amdgcn_readfirstlane((uint32_t)p.progs[a].phase) & 1) << a;
+  const uint64_t all_mask = nprogs >= 64 ? ~0ull : (1ull << nprogs) - 1;
+  // A record's index, function, caller and clocks, loaded one record ahead
+  // and the index two ahead (as k_sys_seq: a lane's walk is no chain of
+  // dependent round trips)
+  struct Rec {
+    uint64_t idx, func, pid, kt_e, kt_r;
+  };
+  auto perm_at = [&](uint64_t kk) -> uint64_t { return kk < end ? (p.perm ? (uint64_t)p.perm[kk] : kk) : 0; };
+  auto fetch = [&](uint64_t kk, uint64_t idx) {
+    Rec f;
+    const bool h = kk < end;
+    f.idx = idx;
+    f.func = h ? p.func[idx] : 0;
+    f.pid = h && p.pid ? p.pid[idx] : p.pid_tgid;
+    f.kt_e = h && p.clock ? p.clock[2 * idx] : 0;
+    f.kt_r = h && p.clock ? p.clock[2 * idx + 1] : 0;
+    return f;
+  };
+  const bool clk = p.clock != nullptr;
+  uint64_t idx_next = perm_at(k + 1);
+  Rec cur = fetch(k, perm_at(k));
+  while (__ballot(k < end) != 0) {
+    const bool has = k < end;
+    const uint64_t idx_next2 = perm_at(k + 2);
+    const Rec nxt = fetch(k + 1, idx_next);
+    const uint64_t idx = cur.idx, pid = cur.pid;
+    // the attached programs of this call's function
+    uint64_t app = 0;
+    for (uint32_t a = 0; a < nprogs; a++) app |= (uint64_t)(has && cur.func == rfl64(p.progs[a].func)) << a;
+    for (uint32_t ph = 0; ph < 2; ph++) {
+      const uint64_t phase_mask = ph ? ret_mask : all_mask & ~ret_mask;
+      const bool need = (app & phase_mask) != 0;
+      if (__ballot(need) == 0) continue;
+      // stage the phase's registers of the wave's records
+      const uint64_t *regs = ph ? p.leave : p.enter;
+      srec[tid] = need ? idx : ~0ull;
+      __syncthreads();
+      for (uint32_t j = tid; j < kW * kUpSeqBlock; j += kUpSeqBlock) {
+        const uint64_t ri = srec[j / kW];
+        if (ri != ~0ull) img[j] = regs[ri * kW + j % kW];
+      }
+      __syncthreads();
+      const uint64_t kt = ph ? cur.kt_r : cur.kt_e;
+      for (uint32_t a = 0; a < nprogs; a++) {
+        if (!((phase_mask >> a) & 1)) continue;
+        const bool run = ((app >> a) & 1) != 0;
+        if (__ballot(run) == 0) continue;
+        const UpSeqProg *sp = &p.progs[a];
+        const uint32_t kind = __builtin_amdgcn_readfirstlane((uint32_t)sp->kind);
+        // each callback on its own copy of the registers: stores through r1
+        // reach neither the records nor the next callback
+        if (run)
+          for (uint32_t w = 0; w < kW; w++) ctx[w] = img[kW * tid + w];
+        c.prog = (prog_ptr)rfl64((uint64_t)(uintptr_t)sp->prog);
+        c.fast = (const FInsn *)rfl64((uint64_t)(uintptr_t)sp->fast);
+        for (int r = 0; r <= 10; r++) c.R[r * kBlock] = 0;
+        c.R[1 * kBlock] = (uint64_t)(uintptr_t)ctx;
+        c.R[2 * kBlock] = kPtRegsBytes;  // sizeof(struct pt_regs), frida_attach_entry.hpp:54-55
+        c.R[10 * kBlock] = stack_top;
+        c.alive = run;
+        c.err = E_OK;
+        c.pc = 0;
+        c.lpc = 0;
+        c.steps = 0;
+        c.unit = idx;
+        int32_t miss_fd = -1;
+        uint64_t miss_hash = 0;
+        uint32_t lru_ops = 0;
+        bool uni = true;
+        while (__ballot(c.alive) != 0) {
+          const uint32_t r = uni ? run_loop<true>(c) : run_loop<false>(c);
+          if (r == R_DONE) break;
+          if (r == R_DIVERGE) {
+            uni = false;
+            continue;
+          }
+          if (r == R_RECONV) {
+            uni = true;
+            continue;
+          }
+          // R_CALL: the helper (dev_helpers.hpp) for the lanes at the call
+          const bool csel = uni ? c.alive : (c.alive && c.lpc == c.call_pc);
+          const uint32_t cid = __builtin_amdgcn_readfirstlane(c.call_id);
+          if (cid == 5 || cid == 14) {
+            // the replay's clock and caller: register values (k_sys_seq)
+            if (csel) c.R[0] = cid == 14 ? pid : clk ? kt : (uint64_t)__builtin_amdgcn_s_memrealtime() * 10ull;
+          } else if (csel) {
+            LaneEnv env;
+            env.vcpu = idx / 64;
+            env.scratch = 0;
+            env.miss_fd = miss_fd;
+            env.miss_hash = miss_hash;
+            env.lru_stamp = (p.lru_seq << kLruSeqShift) | ((idx & 0xffffffffull) << kLruUnitShift);
+            env.lru_ops = lru_ops;
+            env.exact = p.exact != 0;
+            // 58 / 187: an override / replace records at the record's own
+            // index; a plain probe has no return callback and fails its unit
+            env.ovr_state = kind == kUpPlain ? nullptr : p.out_state + idx;
+            env.ovr_val = kind == kUpPlain ? nullptr : p.out_rets + idx;
+            env.ovr_bit = 1;
+            env.pid_tgid = pid;
+            env.kt_on = clk;
+            env.ktime = kt;
+            uint32_t cerr = E_OK;
+            uint64_t *R = c.R;
+            const MemLane ml{stack_top - kStackSize, (uint64_t)(uintptr_t)ctx, kStackSize, kPtRegsBytes};
+            // the attached program's VM's identity and the attachment's own
+            // func_ip / cookie (no recorded stacks: the host refuses 27 / 67)
+            TaskEnv te{};
+            if (cid == 6 || cid == 15 || cid == 16) {
+              const SeqTask *tk = &p.tasks[__builtin_amdgcn_readfirstlane((uint32_t)sp->task) % kSeqMaxTasks];
+              te.uid_gid = tk->uid_gid;
+              for (int j = 0; j < 8; j++) te.comm[j] = tk->comm[j];
+              te.trace_log = p.trace_log;
+              te.trace_cap = p.trace_cap;
+              te.unit = idx;
+            }
+            if (cid == 173) te.func_ip = kind == kUpPlain ? rfl64(sp->func) : 0;
+            if (cid == 174) te.cookie = rfl64(sp->cookie);
+            const uint64_t rv = cid == kTailHelper ? 0
+                                : call_helper<true>(cid, R[1 * kBlock], R[2 * kBlock], R[3 * kBlock], R[4 * kBlock],
+                                              R[5 * kBlock], p.maps, p.ncpu, idx ^ ((uint64_t)c.steps << 40), env,
+                                              &cerr, c.win, ml, te);
+            if (cid == kTailHelper) cerr = E_BADOP;  // (the host refuses such programs)
+            R[0] = rv;
+            miss_fd = env.miss_fd;
+            miss_hash = env.miss_hash;
+            lru_ops = env.lru_ops;
+            if (cerr != E_OK) {
+              c.err = cerr;
+              c.alive = false;
+            }
+          }
+          if (uni)
+            c.pc = c.call_pc + 1;
+          else
+            c.lpc = csel ? c.call_pc + 1 : c.lpc;
+        }
+        // a failed callback is counted; a replace always returns its r0, a
+        // failed one 0 (a failed exec reports r0 = 0: DESIGN.md, Uprobe replay)
+        const bool bad = run && c.err != E_OK;
+        if (bad) atomicAdd(p.err_count, 1u);
+        if (run && kind == kUpReplace) {
+          p.out_state[idx] |= 1u;
+          p.out_rets[idx] = bad ? 0 : (int64_t)c.R[0];
+        }
+      }
+    }
+    if (has) {
+      k++;
+      cur = nxt;
+      idx_next = idx_next2;
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Host-side launch wrappers
 // ---------------------------------------------------------------------------
@@ -1814,6 +2022,13 @@ extern "C" hipError_t bpftime_amd_launch_sys_seq(const SeqParams *p, hipStream_t
   const uint64_t grid = (p->nseg + kBlock - 1) / kBlock;
   if (grid == 0 || grid > 0x7fffffffull || p->nprogs > kSeqMaxProgs) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_sys_seq, dim3((uint32_t)grid), dim3(kBlock), seq_lds_bytes(kBlock, p->fast != 0), stream, *p);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t bpftime_amd_launch_up_seq(const UpSeqParams *p, hipStream_t stream) {
+  const uint64_t grid = (p->nseg + kUpSeqBlock - 1) / kUpSeqBlock;
+  if (grid == 0 || grid > 0x7fffffffull || p->nprogs > kSeqMaxProgs) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_up_seq, dim3((uint32_t)grid), dim3(kUpSeqBlock), 0, stream, *p);
   return hipGetLastError();
 }
 

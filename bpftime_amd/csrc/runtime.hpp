@@ -227,5 +227,21 @@ struct SeqAttach {
 };
 int64_t seq_dispatch(const std::vector<SeqAttach> &progs, const SysLayout &lay, uint64_t n, const uint32_t *perm,
                      const uint32_t *seg, uint64_t nseg, int64_t *out, uint32_t flags, uint32_t *err, hipStream_t s);
+// A loaded VM's task identity as the thread-ordered launches compare it:
+// uid_gid, then the 64 bytes of comm.  -1: no program loaded.
+int vm_task_identity(const ::ebpf_vm *vm, uint64_t out[9]);
+// The thread-ordered uprobe replay's launch (interp.hip k_up_seq): `progs` as
+// uprobe_dispatch.cpp's running() orders them (entry attachments, then return
+// ones); `recs` carries the records, their grouping (perm / seg / nseg as
+// above) and out_state / out_rets, the rest is filled here.  `err` and the
+// return value as seq_dispatch's.
+struct USeqAttach {
+  const ::ebpf_vm *vm;
+  uint64_t func;
+  bool at_return;
+  uint8_t kind;  // common.hpp kUpPlain / kUpOverride / kUpReplace
+};
+int64_t useq_dispatch(const std::vector<USeqAttach> &progs, const UpSeqParams &recs, uint32_t flags, uint32_t *err,
+                      hipStream_t s);
 
 }  // namespace bpftime_amd

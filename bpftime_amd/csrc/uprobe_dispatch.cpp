@@ -17,17 +17,27 @@
 //    and, when it called bpf_override_return / bpf_set_retval, returns that
 //    value in place of the call; a replace always returns the program's r0
 //    (frida_uprobe_attach_impl.cpp:236-263).
-// Here the calls are recorded and every attachment runs once over the
-// records of its function (uprobe_dispatch.hip gathers them), program-major:
-// entry attachments in attach order, then return attachments.  That equals
-// the per-call order when the programs commute; two that may not (the
-// loader's map effects, as the syscall dispatch reads them) are refused.
+// Here the calls are recorded and one of two plans runs them:
+//  * program-major (the default): every attachment runs once over the records
+//    of its function (uprobe_dispatch.hip gathers them), entry attachments in
+//    attach order, then return attachments.  That equals the per-call order
+//    when the programs commute; two that may not (the loader's map effects,
+//    as the syscall dispatch reads them) are refused;
+//  * thread-ordered (BPFTIME_AMD_DISPATCH_THREADS): the records grouped by
+//    their recorded thread (group.hip), one lane per thread walking its calls
+//    in record order, each call's entry callbacks and then its return
+//    callbacks back to back (interp.hip k_up_seq; vm_api.cpp useq_dispatch) --
+//    the reference's schedule, whatever the programs share.  funclatency's
+//    pair is the case (example/tracing/funclatency/funclatency.bpf.c: the
+//    entry probe stores starts[tid], the return probe reads it).  The plan is
+//    opt-in, never taken by itself: the refusal above is pinned behaviour.
 // Host-side bookkeeping only; the work is on the device.
 #include <errno.h>
 #include <stdlib.h>
 #include <sys/syscall.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -38,6 +48,11 @@
 #include "../../include/ebpf-vm.h"
 #include "runtime.hpp"
 #include "uprobe_dispatch.hpp"
+
+extern "C" size_t bpftime_amd_group_scratch_bytes(uint64_t n);
+extern "C" hipError_t bpftime_amd_group_threads(const void *pid, uint64_t stride, uint64_t n, void *scratch,
+                                                uint32_t **perm, uint32_t **seg, uint64_t *nseg,
+                                                hipStream_t stream);
 
 using namespace bpftime_amd;
 
@@ -73,6 +88,7 @@ struct Buf {
 };
 struct StreamBufs {
   Buf counts, rows;
+  Buf group;  // the thread-ordered plan: its failure counter, then the thread grouping
   std::shared_ptr<std::mutex> mu = std::make_shared<std::mutex>();
 };
 std::map<hipStream_t, StreamBufs> g_bufs;
@@ -131,8 +147,51 @@ int first_conflict(const std::vector<Attach> &order, std::string *what) {
   };
   *what = "programs " + who(i) + " and " + who(j) + " may not commute on " +
           (map < 0 ? std::string("a map the loader cannot place") : "map fd " + std::to_string(map)) +
-          ": program-major order would differ from the per-call order (detach one, or dispatch them apart)";
+          ": program-major order would differ from the per-call order (detach one, or dispatch them apart); "
+          "BPFTIME_AMD_DISPATCH_THREADS runs them in the per-call order";
   return 1;
+}
+
+// What the thread-ordered plan does not run, named (empty: nothing)
+std::string threads_refusal(const std::vector<Attach> &order, uint32_t flags) {
+  if (order.size() > kSeqMaxProgs)
+    return std::to_string(order.size()) + " running attachments: the thread-ordered plan holds at most " +
+           std::to_string(kSeqMaxProgs);
+  std::vector<std::vector<uint64_t>> ids;
+  for (const Attach &a : order) {
+    if (a.flags & kProgReadsStacks)
+      return "'" + a.name + "' calls bpf_get_stackid / bpf_get_stack: the STACK_TRACE commit order belongs to the "
+             "program-major plan, the thread-ordered plan does not run it";
+    // lanes in thread order are not record order across threads
+    if (!(flags & EBPF_BATCH_ORDERED) && vm_touches_qs(a.vm.get()))
+      return "'" + a.name + "' touches a QUEUE / STACK map: the thread-ordered plan runs it only with EBPF_BATCH_ORDERED";
+    std::vector<uint64_t> id(9);
+    if (vm_task_identity(a.vm.get(), id.data()) < 0) return "an attached program is not loaded";
+    if (std::find(ids.begin(), ids.end(), id) == ids.end()) ids.push_back(id);
+  }
+  if (ids.size() > kSeqMaxTasks)
+    return "the attached programs' VMs have " + std::to_string(ids.size()) +
+           " distinct task identities: the thread-ordered plan holds at most " + std::to_string(kSeqMaxTasks);
+  return "";
+}
+
+// The plan of a dispatch with these flags over the running attachments
+// (entry, then return): 1 thread-ordered, 0 program-major, -1 a named error
+int plan_for(const std::vector<Attach> &order, uint32_t flags) {
+  const bool threads = (flags & BPFTIME_AMD_DISPATCH_THREADS) != 0;
+  if (threads && (flags & BPFTIME_AMD_DISPATCH_PROGRAMS))
+    return (int)fail("BPFTIME_AMD_DISPATCH_PROGRAMS and BPFTIME_AMD_DISPATCH_THREADS name different plans", EINVAL);
+  if (threads) {
+    const std::string why = threads_refusal(order, flags);
+    return why.empty() ? 1 : (int)fail(why, EINVAL);
+  }
+  if (order.size() > 1) {
+    std::string what;
+    const int c = first_conflict(order, &what);
+    if (c < 0) return (int)fail("an attached program is not loaded", EINVAL);
+    if (c) return (int)fail(what, EINVAL);
+  }
+  return 0;
 }
 
 int attach(int prog_fd, uint64_t func, int kind, const uint64_t *cookie, int link_fd) {
@@ -207,8 +266,8 @@ uint64_t up(uint64_t v) { return (v + 255) & ~255ull; }
 // attachments (bpftime_amd_uprobe_last_ms)
 std::mutex g_time_mu;
 struct Times {
-  float count_ms = 0, gather_ms = 0;
-  uint64_t rows = 0;
+  float count_ms = 0, gather_ms = 0;  // (thread-ordered plan: the grouping, the replay kernel)
+  uint64_t rows = 0;                  // (... and the records)
 } g_times;
 
 // a pair of events around launches on s (no-ops unless `on`)
@@ -332,6 +391,54 @@ int64_t run_one(const Attach &a, bool at_entry, const struct bpftime_amd_call_re
   return rc;
 }
 
+// The thread-ordered plan: group the records by caller, one launch for every
+// attachment (vm_api.cpp useq_dispatch).  >= 0 failed callbacks (SYNC), -1 error.
+int64_t dispatch_threads(const std::vector<Attach> &order, size_t nentry, const struct bpftime_amd_call_records *r,
+                         uint32_t *out_state, int64_t *out_rets, uint32_t flags, StreamBufs &sb, hipStream_t s) {
+  const uint64_t n = r->count;
+  std::vector<USeqAttach> progs;
+  for (size_t i = 0; i < order.size(); i++) {
+    const int k = order[i].kind;
+    progs.push_back({order[i].vm.get(), order[i].func, i >= nentry,
+                     k == BPFTIME_AMD_UREPLACE ? kUpReplace : k == BPFTIME_AMD_UPROBE_OVERRIDE ? kUpOverride : kUpPlain});
+  }
+  // one thread: an ORDERED dispatch (the serial reference run) or records
+  // without a recorded caller (every call is the dispatching thread's)
+  const bool one = (flags & EBPF_BATCH_ORDERED) || !r->pid_tgid;
+  const uint64_t gbytes = one ? 0 : bpftime_amd_group_scratch_bytes(n);
+  if (!one && !gbytes) return fail("thread grouping of " + std::to_string(n) + " records", EINVAL);
+  uint8_t *buf = grow(sb.group, 256 + gbytes, s);
+  if (!buf) return fail("scratch allocation failed", ENOMEM);
+  const bool timed = (flags & EBPF_BATCH_TIMED) != 0;
+  UpSeqParams p{};
+  p.nseg = 1;
+  Span t_group(timed, s);
+  if (!one) {
+    const hipError_t e = bpftime_amd_group_threads(r->pid_tgid, 8, n, buf + 256, const_cast<uint32_t **>(&p.perm),
+                                                   const_cast<uint32_t **>(&p.seg), &p.nseg, s);
+    if (e != hipSuccess) return fail(std::string("thread grouping: ") + hipGetErrorString(e), EIO);
+  }
+  t_group.end();
+  p.n = n;
+  p.enter = (const uint64_t *)r->enter;
+  p.leave = (const uint64_t *)r->leave;
+  p.func = r->func;
+  p.pid = r->pid_tgid;
+  p.clock = (const uint64_t *)r->clock;
+  p.out_state = out_state;
+  p.out_rets = out_rets;
+  Span t_run(timed, s);
+  const int64_t rc = useq_dispatch(progs, p, flags, (uint32_t *)buf, s);
+  t_run.end();
+  if (rc >= 0 && timed && hipStreamSynchronize(s) == hipSuccess) {
+    std::lock_guard<std::mutex> tg(g_time_mu);
+    g_times.count_ms = t_group.ms();
+    g_times.gather_ms = t_run.ms();
+    g_times.rows = n;
+  }
+  return rc;
+}
+
 }  // namespace
 
 void bpftime_amd::uprobe_detach_all() {
@@ -422,6 +529,13 @@ int bpftime_amd_uprobe_last_ms(float *count_ms, float *gather_ms, uint64_t *rows
   return 0;
 }
 
+int bpftime_amd_uprobe_dispatch_plan(uint32_t flags) {
+  std::vector<Attach> order, leave;
+  running(order, leave);
+  order.insert(order.end(), leave.begin(), leave.end());
+  return plan_for(order, flags);
+}
+
 int64_t bpftime_amd_uprobe_dispatch(const struct bpftime_amd_call_records *r, uint32_t *out_state, int64_t *out_rets,
                                     uint32_t flags, void *stream) {
   if (!r) return fail("no records", EINVAL);
@@ -443,12 +557,8 @@ int64_t bpftime_amd_uprobe_dispatch(const struct bpftime_amd_call_records *r, ui
     return fail("override / replace programs are attached: out_state and out_rets are needed", EINVAL);
   std::vector<Attach> order = entry;
   order.insert(order.end(), leave.begin(), leave.end());
-  if (order.size() > 1) {
-    std::string what;
-    const int c = first_conflict(order, &what);
-    if (c < 0) return fail("an attached program is not loaded", EINVAL);
-    if (c) return fail(what, EINVAL);
-  }
+  const int plan = plan_for(order, flags);
+  if (plan < 0) return -1;
   if (r->count == 0 || order.empty()) return 0;
   hipStream_t s = (hipStream_t)stream;
   StreamBufs *sb;
@@ -463,6 +573,7 @@ int64_t bpftime_amd_uprobe_dispatch(const struct bpftime_amd_call_records *r, ui
     std::lock_guard<std::mutex> tg(g_time_mu);
     g_times = Times();
   }
+  if (plan) return dispatch_threads(order, entry.size(), r, out_state, out_rets, flags, *sb, s);
   int64_t failed = 0;
   for (size_t i = 0; i < order.size(); i++) {
     const int64_t rc = run_one(order[i], i < entry.size(), r, out_state, out_rets, flags, *sb, s);

@@ -1564,78 +1564,73 @@ bool vm_touches_qs(const ::ebpf_vm *vm) {
 }
 
 extern "C" hipError_t bpftime_amd_launch_sys_seq(const SeqParams *p, hipStream_t stream);
+extern "C" hipError_t bpftime_amd_launch_up_seq(const UpSeqParams *p, hipStream_t stream);
 
-int64_t seq_dispatch(const std::vector<SeqAttach> &progs, const SysLayout &lay, uint64_t n, const uint32_t *perm,
-                     const uint32_t *seg, uint64_t nseg, int64_t *out, uint32_t flags, uint32_t *err, hipStream_t s) {
-  auto fail = [](const std::string &e) {
-    set_error("thread-ordered dispatch: " + e);
-    return (int64_t)-1;
-  };
-  if (progs.size() > kSeqMaxProgs)
-    return fail(std::to_string(progs.size()) + " programs attached (at most " + std::to_string(kSeqMaxProgs) + ")");
+namespace {
+// What the thread-ordered launches (k_sys_seq, k_up_seq) share: per attached
+// program the checks and the upkeep flags exec_batch derives for one launch,
+// the table of task identities, and the map upkeep around the one launch that
+// runs them all
+struct SeqLaunch {
   Runtime &r = rt();
-  SeqParams p{};
+  const bool ordered;
   // the images stay referenced until the launch is queued (a relink by
   // another thread never frees what is read: Image, above)
   std::vector<std::shared_ptr<Image>> keep;
-  const bool ordered = (flags & EBPF_BATCH_ORDERED) != 0;
-  bool may_delete = false, names_lpm = false, qs_adds = false, qs_takes = false;
+  bool may_delete = false, names_lpm = false, qs_adds = false, qs_takes = false, touches_lpm = false;
   std::vector<int> lpm_w;
   uint32_t lpm_updates = 0;
   uint64_t steps = 0;
   uint32_t ntasks = 0;
-  // the asm tier runs the callbacks when every stack fits the LDS stacks and
-  // the threads are at most kSeqAsmThreads: measured (profiles/
-  // r06_seq_xover.txt, syscount's pair) 2-3.7x the C++ tier up to 8192
-  // threads, even at 16384, and behind it from 32768 on, where the waves no
-  // longer wait on their own latency chains and the map helpers' coherent
-  // atomics set the rate.  BPFTIME_AMD_SEQ_ASM=1 / 0 forces a tier.
-  const char *asm_env = getenv("BPFTIME_AMD_SEQ_ASM");
-  bool fast = asm_env && asm_env[0] ? asm_env[0] != '0' : nseg <= kSeqAsmThreads;
+  std::unique_lock<std::mutex> lpm_lk;
+  std::string err;  // why the last call returned false / -1
+
+  explicit SeqLaunch(bool ordered_) : ordered(ordered_), lpm_lk(rt().lpm_launch_mu, std::defer_lock) {}
+
+  bool fail(const std::string &e) {
+    err = e;
+    return false;
+  }
+
   // constant-address loads (loader.cpp const_loads: array storage nothing in
   // THAT program writes) stay scalar-cache loads only while no attached
   // program writes or adds to an array map: one launch runs them all
-  bool array_writes = false;
-  for (const SeqAttach &a : progs) {
-    auto im = a.vm->impl->image();
-    if (!im) continue;
-    fast = fast && !im->prog.big_stack && im->prog.stack_size <= kLdsStackMax;
-    const uint8_t w = FX_WRITE | FX_ADD;
-    array_writes = array_writes || (im->fr.any_fx & w);
-    for (const auto &kv : im->fr.map_fx)
-      if ((kv.second & w) && kv.first >= 0 && kv.first < (int32_t)kMaxFds &&
-          (r.maps[kv.first].type == MT_ARRAY || r.maps[kv.first].type == MT_PERCPU_ARRAY))
-        array_writes = true;
+  bool array_writes(const std::vector<const ::ebpf_vm *> &vms) {
+    bool any = false;
+    for (const ::ebpf_vm *v : vms) {
+      auto im = v->impl->image();
+      if (!im) continue;
+      const uint8_t w = FX_WRITE | FX_ADD;
+      any = any || (im->fr.any_fx & w);
+      for (const auto &kv : im->fr.map_fx)
+        if ((kv.second & w) && kv.first >= 0 && kv.first < (int32_t)kMaxFds &&
+            (r.maps[kv.first].type == MT_ARRAY || r.maps[kv.first].type == MT_PERCPU_ARRAY))
+          any = true;
+    }
+    return any;
   }
-  for (const SeqAttach &a : progs) {
-    Mi355xVm *vm = a.vm->impl;
+
+  // One attached program: its image and ORDERED link, and the index of its
+  // VM's identity in `tasks` (one table entry per distinct identity)
+  bool add(Mi355xVm *vm, bool no_kldx, bool fast, SeqTask *tasks, const DInsn *&prog, const FInsn *&link,
+           uint32_t &task) {
     auto im = vm->image();
     if (!vm->loaded || !im) return fail("an attached program is not loaded");
     if (vm->has_tail) return fail("an attached program calls bpf_tail_call (program-major dispatch runs it)");
-    const FInsn *f = im->linked(false, false, 0, 0, true, -1, 0, 0, array_writes && progs.size() > 1, fast);
-    if (!f) return fail("device upload failed");
-    SeqProg &q = p.progs[p.nprogs++];
-    q.prog = im->d_prog;
-    q.fast = f;
-    q.sys_nr = a.sys_nr;
-    q.enter = a.enter ? 1 : 0;
-    {  // its VM's identity: one table entry per distinct identity
-      SeqTask tk{};
-      vm->task_into(tk.uid_gid, tk.comm);
-      uint32_t ti = 0;
-      while (ti < ntasks && memcmp(&p.tasks[ti], &tk, sizeof(tk)) != 0) ti++;
-      if (ti == ntasks) {
-        if (ntasks == kSeqMaxTasks)
-          return fail("the attached programs' VMs have more than " + std::to_string(kSeqMaxTasks) +
-                      " distinct task identities");
-        p.tasks[ntasks++] = tk;
-      }
-      q.task = ti;
+    link = im->linked(false, false, 0, 0, true, -1, 0, 0, no_kldx, fast);
+    if (!link) return fail("device upload failed");
+    prog = im->d_prog;
+    SeqTask tk{};
+    vm->task_into(tk.uid_gid, tk.comm);
+    uint32_t ti = 0;
+    while (ti < ntasks && memcmp(&tasks[ti], &tk, sizeof(tk)) != 0) ti++;
+    if (ti == ntasks) {
+      if (ntasks == kSeqMaxTasks)
+        return fail("the attached programs' VMs have more than " + std::to_string(kSeqMaxTasks) +
+                    " distinct task identities");
+      tasks[ntasks++] = tk;
     }
-    {  // its attach cookie (a link's; a syscall tracepoint has no func_ip)
-      uint64_t ip;
-      vm->attach_into(ip, p.cookies[p.nprogs - 1]);
-    }
+    task = ti;
     may_delete |= im->prog.may_delete;
     names_lpm |= im->fr.names_lpm;
     {  // ARRAY_OF_MAPS: the inner maps its slots name (as exec_batch)
@@ -1663,7 +1658,113 @@ int64_t seq_dispatch(const std::vector<SeqAttach> &progs, const SysLayout &lay, 
     }
     steps = std::max(steps, vm->step_limit);
     keep.push_back(std::move(im));
+    return true;
   }
+
+  // the map upkeep exec_batch does before a launch, for the union of the
+  // programs (a deletion never runs beside a cached launch; LPM launches
+  // under the LPM launch lock; lookup indexes; LRU stamps; host views)
+  bool before(uint64_t n, uint64_t &lru_seq) {
+    if (may_delete && r.lcache_inflight.load()) {
+      if (hipDeviceSynchronize() != hipSuccess) return fail("device synchronize failed");
+      r.lcache_inflight = false;
+      r.deleter_inflight = false;
+    }
+    if (!qs_launch_fence(qs_adds, qs_takes)) return fail("device synchronize failed");
+    touches_lpm = r.lpm_maps.load() > 0 && names_lpm;
+    if (touches_lpm) {
+      lpm_lk.lock();
+      if ((!lpm_w.empty() && r.lpm_inflight.load()) || r.lpm_writer_inflight.load()) {
+        if (hipDeviceSynchronize() != hipSuccess) return fail("device synchronize failed");
+        r.lpm_inflight = false;
+        r.lpm_writer_inflight = false;
+      }
+    }
+    if (r.prepare_ix(may_delete, n, lpm_w, lpm_updates, names_lpm) < 0) {
+      const std::string le = bpftime_amd_last_error() ? bpftime_amd_last_error() : "";
+      return fail(le.rfind("LPM_TRIE", 0) == 0 ? le : "hash lookup index rebuild failed");
+    }
+    lru_seq = r.prepare_lru();
+    if (!lru_seq) return fail("LRU table upkeep failed");
+    if (r.host_views_push() < 0) return fail("host view upload failed");
+    return true;
+  }
+
+  // (the launch is queued)
+  void after() {
+    if (may_delete) r.deleter_inflight = true;
+    if (qs_adds) r.qs_adder_inflight = true;
+    if (qs_takes) r.qs_taker_inflight = true;
+    if (!lpm_w.empty()) {
+      std::lock_guard<std::mutex> g(r.mu);
+      for (const int fd : lpm_w) r.lpm_dev_dirty.insert(fd);
+      r.lpm_writer_inflight = true;
+    }
+    if (touches_lpm) {
+      r.lpm_inflight = true;
+      lpm_lk.unlock();
+    }
+  }
+
+  // EBPF_BATCH_SYNC: the failed callbacks (`counter`: the launch's device
+  // u32), the host views and written tries pulled; -1 with `err` (empty: the
+  // pull set the runtime's error itself)
+  int64_t finish(uint32_t *counter, hipStream_t s) {
+    uint32_t failed = 0;
+    hipError_t e = hipMemcpyAsync(&failed, counter, 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess || r.host_views_pull() < 0) {
+      fail(std::string("sync failed: ") + (e != hipSuccess ? hipGetErrorString(e) : "host view pull"));
+      return -1;
+    }
+    for (const int fd : lpm_w) {
+      std::lock_guard<std::mutex> g(r.mu);
+      if (lpm_pull(fd) < 0) {
+        err.clear();
+        return -1;
+      }
+    }
+    return failed;
+  }
+};
+}  // namespace
+
+int64_t seq_dispatch(const std::vector<SeqAttach> &progs, const SysLayout &lay, uint64_t n, const uint32_t *perm,
+                     const uint32_t *seg, uint64_t nseg, int64_t *out, uint32_t flags, uint32_t *err, hipStream_t s) {
+  auto fail = [](const std::string &e) {
+    if (!e.empty()) set_error("thread-ordered dispatch: " + e);
+    return (int64_t)-1;
+  };
+  if (progs.size() > kSeqMaxProgs)
+    return fail(std::to_string(progs.size()) + " programs attached (at most " + std::to_string(kSeqMaxProgs) + ")");
+  SeqParams p{};
+  SeqLaunch L((flags & EBPF_BATCH_ORDERED) != 0);
+  // the asm tier runs the callbacks when every stack fits the LDS stacks and
+  // the threads are at most kSeqAsmThreads: measured (profiles/
+  // r06_seq_xover.txt, syscount's pair) 2-3.7x the C++ tier up to 8192
+  // threads, even at 16384, and behind it from 32768 on, where the waves no
+  // longer wait on their own latency chains and the map helpers' coherent
+  // atomics set the rate.  BPFTIME_AMD_SEQ_ASM=1 / 0 forces a tier.
+  const char *asm_env = getenv("BPFTIME_AMD_SEQ_ASM");
+  bool fast = asm_env && asm_env[0] ? asm_env[0] != '0' : nseg <= kSeqAsmThreads;
+  std::vector<const ::ebpf_vm *> vms;
+  for (const SeqAttach &a : progs) {
+    vms.push_back(a.vm);
+    auto im = a.vm->impl->image();
+    if (!im) continue;
+    fast = fast && !im->prog.big_stack && im->prog.stack_size <= kLdsStackMax;
+  }
+  const bool no_kldx = L.array_writes(vms) && progs.size() > 1;
+  for (const SeqAttach &a : progs) {
+    SeqProg &q = p.progs[p.nprogs++];
+    if (!L.add(a.vm->impl, no_kldx, fast, p.tasks, q.prog, q.fast, q.task)) return fail(L.err);
+    q.sys_nr = a.sys_nr;
+    q.enter = a.enter ? 1 : 0;
+    // its attach cookie (a link's; a syscall tracepoint has no func_ip)
+    uint64_t ip;
+    a.vm->impl->attach_into(ip, p.cookies[p.nprogs - 1]);
+  }
+  Runtime &r = L.r;
   p.lay = lay;
   p.n = n;
   p.perm = perm;
@@ -1675,65 +1776,75 @@ int64_t seq_dispatch(const std::vector<SeqAttach> &progs, const SysLayout &lay, 
   p.checked = (flags & EBPF_BATCH_UNCHECKED) ? 0 : 1;
   p.arena_lo = (uint64_t)(uintptr_t)r.arena;
   p.arena_hi = p.arena_lo + r.arena_size;
-  p.step_limit = steps;
+  p.step_limit = L.steps;
   p.pid_tgid = ((uint64_t)(uint32_t)getpid() << 32) | (uint32_t)syscall(SYS_gettid);
   p.err_count = err;
   p.trace_log = trace_log().d;
   p.trace_cap = trace_log().cap;
-  p.exact = ordered ? 1 : 0;
+  p.exact = L.ordered ? 1 : 0;
   p.fast = fast ? 1 : 0;
-  // the map upkeep exec_batch does before a launch, for the union of the
-  // programs (a deletion never runs beside a cached launch; LPM launches
-  // under the LPM launch lock; lookup indexes; LRU stamps; host views)
-  if (may_delete && r.lcache_inflight.load()) {
-    if (hipDeviceSynchronize() != hipSuccess) return fail("device synchronize failed");
-    r.lcache_inflight = false;
-    r.deleter_inflight = false;
-  }
-  if (!qs_launch_fence(qs_adds, qs_takes)) return fail("device synchronize failed");
-  std::unique_lock<std::mutex> lpm_lk(r.lpm_launch_mu, std::defer_lock);
-  const bool touches_lpm = r.lpm_maps.load() > 0 && names_lpm;
-  if (touches_lpm) {
-    lpm_lk.lock();
-    if ((!lpm_w.empty() && r.lpm_inflight.load()) || r.lpm_writer_inflight.load()) {
-      if (hipDeviceSynchronize() != hipSuccess) return fail("device synchronize failed");
-      r.lpm_inflight = false;
-      r.lpm_writer_inflight = false;
-    }
-  }
-  if (r.prepare_ix(may_delete, n, lpm_w, lpm_updates, names_lpm) < 0) {
-    const std::string le = bpftime_amd_last_error() ? bpftime_amd_last_error() : "";
-    return fail(le.rfind("LPM_TRIE", 0) == 0 ? le : "hash lookup index rebuild failed");
-  }
-  p.lru_seq = r.prepare_lru();
-  if (!p.lru_seq) return fail("LRU table upkeep failed");
-  if (r.host_views_push() < 0) return fail("host view upload failed");
+  if (!L.before(n, p.lru_seq)) return fail(L.err);
   hipError_t e = hipMemsetAsync(err, 0, 4, s);
   if (e == hipSuccess) e = bpftime_amd_launch_sys_seq(&p, s);
   if (e != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(e));
-  if (may_delete) r.deleter_inflight = true;
-  if (qs_adds) r.qs_adder_inflight = true;
-  if (qs_takes) r.qs_taker_inflight = true;
-  if (!lpm_w.empty()) {
-    std::lock_guard<std::mutex> g(r.mu);
-    for (const int fd : lpm_w) r.lpm_dev_dirty.insert(fd);
-    r.lpm_writer_inflight = true;
-  }
-  if (touches_lpm) {
-    r.lpm_inflight = true;
-    lpm_lk.unlock();
-  }
+  L.after();
   if (!(flags & EBPF_BATCH_SYNC)) return 0;
-  uint32_t failed = 0;
-  e = hipMemcpyAsync(&failed, err, 4, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess || r.host_views_pull() < 0)
-    return fail(std::string("sync failed: ") + (e != hipSuccess ? hipGetErrorString(e) : "host view pull"));
-  for (const int fd : lpm_w) {
-    std::lock_guard<std::mutex> g(r.mu);
-    if (lpm_pull(fd) < 0) return -1;
+  const int64_t failed = L.finish(err, s);
+  return failed < 0 ? fail(L.err) : failed;
+}
+
+int vm_task_identity(const ::ebpf_vm *vm, uint64_t out[9]) {
+  if (!vm || !vm->impl->loaded) return -1;
+  vm->impl->task_into(out[0], out + 1);
+  return 0;
+}
+
+int64_t useq_dispatch(const std::vector<USeqAttach> &progs, const UpSeqParams &recs, uint32_t flags, uint32_t *err,
+                      hipStream_t s) {
+  auto fail = [](const std::string &e) {
+    if (!e.empty()) set_error("thread-ordered dispatch: " + e);
+    return (int64_t)-1;
+  };
+  if (progs.size() > kSeqMaxProgs)
+    return fail(std::to_string(progs.size()) + " programs attached (at most " + std::to_string(kSeqMaxProgs) + ")");
+  UpSeqParams p = recs;  // (the records, their grouping and the outputs: uprobe_dispatch.cpp)
+  p.nprogs = 0;
+  SeqLaunch L((flags & EBPF_BATCH_ORDERED) != 0);
+  std::vector<const ::ebpf_vm *> vms;
+  for (const USeqAttach &a : progs) vms.push_back(a.vm);
+  const bool no_kldx = L.array_writes(vms) && progs.size() > 1;
+  for (const USeqAttach &a : progs) {
+    UpSeqProg &q = p.progs[p.nprogs++];
+    uint32_t task = 0;
+    // (the C++ tier only: private stacks, no LDS-stack link)
+    if (!L.add(a.vm->impl, no_kldx, false, p.tasks, q.prog, q.fast, task)) return fail(L.err);
+    q.task = (uint16_t)task;
+    q.func = a.func;
+    q.phase = a.at_return ? 1 : 0;
+    q.kind = a.kind;
+    uint64_t ip;  // (attach() set it to what kind and func say: common.hpp UpSeqProg)
+    a.vm->impl->attach_into(ip, q.cookie);
   }
-  return failed;
+  Runtime &r = L.r;
+  p.maps = r.d_maptab;
+  p.ncpu = r.ncpu;
+  p.checked = (flags & EBPF_BATCH_UNCHECKED) ? 0 : 1;
+  p.arena_lo = (uint64_t)(uintptr_t)r.arena;
+  p.arena_hi = p.arena_lo + r.arena_size;
+  p.step_limit = L.steps;
+  p.pid_tgid = ((uint64_t)(uint32_t)getpid() << 32) | (uint32_t)syscall(SYS_gettid);
+  p.err_count = err;
+  p.trace_log = trace_log().d;
+  p.trace_cap = trace_log().cap;
+  p.exact = L.ordered ? 1 : 0;
+  if (!L.before(p.n, p.lru_seq)) return fail(L.err);
+  hipError_t e = hipMemsetAsync(err, 0, 4, s);
+  if (e == hipSuccess) e = bpftime_amd_launch_up_seq(&p, s);
+  if (e != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(e));
+  L.after();
+  if (!(flags & EBPF_BATCH_SYNC)) return 0;
+  const int64_t failed = L.finish(err, s);
+  return failed < 0 ? fail(L.err) : failed;
 }
 }  // namespace bpftime_amd
 

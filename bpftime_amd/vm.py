@@ -581,6 +581,10 @@ def uprobe_dispatch(func: Optional[DeviceBuffer], n: int, enter: Optional[Device
     bpftime_amd_call_records): func (u64 per call), enter / leave (168-B
     pt_regs per call), pid_tgid (u64), clock (2 x u64), the stacks as
     exec_batch's; out_state (u32) / out_rets (i64) receive the overrides.
+    flags: BATCH_* and the plan -- program-major by default and with
+    DISPATCH_PROGRAMS (a pair that may not commute is refused), thread-ordered
+    with DISPATCH_THREADS (| BATCH_ORDERED: one lane, the serial run); both
+    plan flags are an error (uprobe_dispatch_plan).
     Returns the failed callbacks (BATCH_SYNC)."""
     p = lambda b: b.ptr if b else None  # noqa: E731
     r = CallRecords(enter=p(enter), leave=p(leave), func=p(func), pid_tgid=p(pid_tgid), clock=p(clock),
@@ -590,6 +594,16 @@ def uprobe_dispatch(func: Optional[DeviceBuffer], n: int, enter: Optional[Device
     rc = lib().bpftime_amd_uprobe_dispatch(C.byref(r), p(out_state), p(out_rets), flags, stream or None)
     if rc < 0:
         raise EbpfError(f"uprobe dispatch failed: {_err()}")
+    return rc
+
+
+def uprobe_dispatch_plan(flags: int = 0) -> int:
+    """1 when a uprobe dispatch with these flags runs thread-ordered for the
+    current attachments, 0 program-major; raises with the named error such a
+    dispatch would give."""
+    rc = lib().bpftime_amd_uprobe_dispatch_plan(flags)
+    if rc < 0:
+        raise EbpfError(f"uprobe dispatch plan failed: {_err()}")
     return rc
 
 

@@ -593,7 +593,17 @@ struct bpftime_amd_call_records {
   uint32_t stack_fixed_depth, stack_max_depth;
   uint64_t count;
 };
-/* Runs every attachment over the records, program-major: the entry
+/* Runs every attachment over the records, by one of two plans.  The plan is
+ * the caller's choice and never automatic (the refusal below is behaviour
+ * hosts rely on); bpftime_amd_uprobe_dispatch_plan tells it beforehand:
+ *   flags                          plan
+ *   neither plan flag              program-major; a pair that may not commute is refused
+ *   BPFTIME_AMD_DISPATCH_PROGRAMS  the same
+ *   BPFTIME_AMD_DISPATCH_THREADS   thread-ordered, whatever the programs share
+ *   ... | EBPF_BATCH_ORDERED       thread-ordered with one lane over every record in
+ *                                  record order: the serial reference run
+ *   both plan flags                -1, EINVAL
+ * Program-major: the entry
  * attachments in attach order, then the return attachments.  Per attachment
  * the records of its function are gathered, in record order, into compact
  * 192-B rows {pt_regs, pid_tgid, the phase's clock, record index} and the
@@ -609,7 +619,24 @@ struct bpftime_amd_call_records {
  * the map.  A dispatch with a single attachment takes EBPF_BATCH_ORDERED and
  * gives the serial result.  Flags: EBPF_BATCH_SYNC / _ORDERED / _UNCHECKED /
  * _TIMED.
- * The call is never fully asynchronous: per attachment the host waits on the
+ * Thread-ordered (funclatency's starts[tid] pair, example/tracing/funclatency/
+ * funclatency.bpf.c, is the case): the records are grouped by pid_tgid (NULL:
+ * one thread owns them all) and one lane per thread walks its calls in record
+ * order; per call the entry callbacks of its function run in attach order,
+ * then its return callbacks (frida_internal_attach_entry.cpp:221-239), which
+ * attachments run at a function decided as above.  Threads are unordered
+ * against each other, as in the reference; a call's return never follows
+ * another call's entry (no nesting).  Every callback gets a fresh copy of the
+ * phase's pt_regs, the record's caller and clock[i][phase], its attachment's
+ * func_ip / cookie and its VM's task identity; counter adds reach memory at
+ * once, so a thread's later callback sees its earlier one; out_state /
+ * out_rets are written as above, at the record's index.  Nothing is refused
+ * for not commuting.  Refused, before any launch: a program that calls
+ * bpf_get_stackid / bpf_get_stack (27 / 67); one that touches a QUEUE / STACK
+ * map, unless EBPF_BATCH_ORDERED is set; more than 64 running attachments;
+ * more than 16 distinct task identities among them.  The host waits on the
+ * stream once, for the grouping's thread count.
+ * Program-major, the call is never fully asynchronous: per attachment the host waits on the
  * stream once, to read how many records matched (it sizes the rows and the
  * batch from that count, and launches nothing for 0).  Without EBPF_BATCH_SYNC
  * only the last attachment's batch and scatter are left in flight.
@@ -623,9 +650,15 @@ struct bpftime_amd_call_records {
  * attachment without out_state / out_rets. */
 int64_t bpftime_amd_uprobe_dispatch(const struct bpftime_amd_call_records *r, uint32_t *out_state,
                                     int64_t *out_rets, uint32_t flags, void *stream);
+/* The plan a dispatch with these flags takes for the current attachments: 1
+ * thread-ordered, 0 program-major, -1 with the named error such a dispatch
+ * would give (both plan flags, a pair that may not commute, a thread-ordered
+ * refusal). */
+int bpftime_amd_uprobe_dispatch_plan(uint32_t flags);
 /* The last EBPF_BATCH_TIMED dispatch, summed over its attachments: the time of
  * the count + scan launches, of the gather launches (ms, stream events), and
- * the rows gathered.  Any out pointer may be NULL. */
+ * the rows gathered.  After a thread-ordered dispatch: the thread grouping's
+ * time, the replay launch's, and the records.  Any out pointer may be NULL. */
 int bpftime_amd_uprobe_last_ms(float *count_ms, float *gather_ms, uint64_t *rows);
 
 /* ---- attach plugins (attach/base_attach_impl/base_attach_impl.hpp:24-71,
