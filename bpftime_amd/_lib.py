@@ -169,6 +169,8 @@ SIGNATURES = [
     ("bpftime_amd_uprobe_detach", C.c_int, [C.c_int]),
     ("bpftime_amd_uprobe_dispatch", C.c_int64, [C.POINTER(CallRecords), C.c_void_p, C.c_void_p, C.c_uint32,
                                                 C.c_void_p]),
+    ("bpftime_amd_uprobe_dispatch_events", C.c_int64, [C.POINTER(CallRecords), C.c_void_p, C.c_uint64, C.c_void_p,
+                                                       C.c_void_p, C.c_uint32, C.c_void_p]),
     ("bpftime_amd_uprobe_dispatch_plan", C.c_int, [C.c_uint32]),
     ("bpftime_amd_uprobe_last_ms", C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), u64p]),
     ("bpftime_amd_enable_trace_printk", C.c_int, [C.c_int]),

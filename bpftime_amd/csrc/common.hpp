@@ -614,7 +614,7 @@ constexpr uint32_t kUpSeqBlock = 64;
 struct UpSeqParams {
   uint32_t nprogs;
   uint32_t exact;         // one lane over every record (EBPF_BATCH_ORDERED)
-  uint64_t n;
+  uint64_t n;             // the walked items: records, or events (below)
   // the records (include/bpftime_amd.h bpftime_amd_call_records), by index:
   const uint64_t *enter;  // n x 21 u64 (null: no entry program runs)
   const uint64_t *leave;  // n x 21 u64 (null: no return program runs)
@@ -640,6 +640,14 @@ struct UpSeqParams {
   uint64_t trace_cap;
   UpSeqProg progs[kSeqMaxProgs];  // in the kernel arguments: scalar loads, no upload
   SeqTask tasks[kSeqMaxTasks];
+  // The event list (bpftime_amd_uprobe_dispatch_events; k_up_seq<true>): 1 when
+  // the walked words are events, (record index << 1) | phase, not record
+  // indexes.  Then n counts events, perm is never null (the grouped event
+  // words, or the caller's list itself for one thread) and nrec is the record
+  // count: a word whose record is not below it runs nothing
+  uint32_t events;
+  uint32_t pad;
+  uint64_t nrec;
 };
 static_assert(sizeof(UpSeqParams) <= 4096, "kernel arguments");
 

@@ -1769,6 +1769,15 @@ extern "C" int bpftime_amd_seq_prof(unsigned long long *out, int reset) {
 // lane's 21 words from the image inside LDS.  The callbacks run in the C++
 // tier (run_loop, private 512-B stacks) with the ORDERED links, as k_sys_seq's
 // C++ tier does; there is no asm tier here.
+//
+// kEvents (bpftime_amd_uprobe_dispatch_events): the walked words are events,
+// (record << 1) | phase, in the thread's recorded order, so a nested or
+// recursive call's return runs after the entries recorded inside it.  Only the
+// walk differs: a lane's item is one phase of one record, and in the phase
+// loop a lane takes part in its own event's phase alone.  A wave whose lanes
+// are all at one phase stages once, a mixed wave twice; the __ballot guards
+// are wave-uniform, so all 64 lanes reach both barriers of either pass.
+template <bool kEvents>
 __global__ __launch_bounds__(kUpSeqBlock) void k_up_seq(UpSeqParams p) {
   constexpr uint32_t kW = kPtRegsBytes / 8;
   // r0..r10 columns and the dummy slot, at run_loop's column stride (kBlock)
@@ -1809,18 +1818,30 @@ __global__ __launch_bounds__(kUpSeqBlock) void k_up_seq(UpSeqParams p) {
   // A record's index, function, caller and clocks, loaded one record ahead
   // and the index two ahead (as k_sys_seq: a lane's walk is no chain of
   // dependent round trips)
+  // (kEvents: the walked word is an event, prefetched two ahead as the index
+  // is; its record's function, caller and the clock of its phase -- kt_e,
+  // whichever phase -- one ahead.  A word whose record is out of range, which
+  // the host refuses beforehand, is an item that runs nothing: `live`)
   struct Rec {
     uint64_t idx, func, pid, kt_e, kt_r;
+    uint32_t ph;
+    bool live;
   };
-  auto perm_at = [&](uint64_t kk) -> uint64_t { return kk < end ? (p.perm ? (uint64_t)p.perm[kk] : kk) : 0; };
-  auto fetch = [&](uint64_t kk, uint64_t idx) {
+  auto perm_at = [&](uint64_t kk) -> uint64_t {
+    if (kEvents) return kk < end ? (uint64_t)p.perm[kk] : 0;
+    return kk < end ? (p.perm ? (uint64_t)p.perm[kk] : kk) : 0;
+  };
+  auto fetch = [&](uint64_t kk, uint64_t word) {
     Rec f;
-    const bool h = kk < end;
+    const uint64_t idx = kEvents ? word >> 1 : word;
+    const bool h = kEvents ? kk < end && idx < p.nrec : kk < end;
     f.idx = idx;
+    f.ph = kEvents ? (uint32_t)word & 1u : 0;
+    f.live = h;
     f.func = h ? p.func[idx] : 0;
     f.pid = h && p.pid ? p.pid[idx] : p.pid_tgid;
-    f.kt_e = h && p.clock ? p.clock[2 * idx] : 0;
-    f.kt_r = h && p.clock ? p.clock[2 * idx + 1] : 0;
+    f.kt_e = h && p.clock ? p.clock[2 * idx + f.ph] : 0;
+    f.kt_r = !kEvents && h && p.clock ? p.clock[2 * idx + 1] : 0;
     return f;
   };
   const bool clk = p.clock != nullptr;
@@ -1833,10 +1854,12 @@ __global__ __launch_bounds__(kUpSeqBlock) void k_up_seq(UpSeqParams p) {
     const uint64_t idx = cur.idx, pid = cur.pid;
     // the attached programs of this call's function
     uint64_t app = 0;
-    for (uint32_t a = 0; a < nprogs; a++) app |= (uint64_t)(has && cur.func == rfl64(p.progs[a].func)) << a;
+    const bool live = kEvents ? has && cur.live : has;
+    for (uint32_t a = 0; a < nprogs; a++) app |= (uint64_t)(live && cur.func == rfl64(p.progs[a].func)) << a;
     for (uint32_t ph = 0; ph < 2; ph++) {
       const uint64_t phase_mask = ph ? ret_mask : all_mask & ~ret_mask;
-      const bool need = (app & phase_mask) != 0;
+      // (kEvents: the lane's event is one phase of its record)
+      const bool need = (!kEvents || cur.ph == ph) && (app & phase_mask) != 0;
       if (__ballot(need) == 0) continue;
       // stage the phase's registers of the wave's records
       const uint64_t *regs = ph ? p.leave : p.enter;
@@ -1847,10 +1870,10 @@ __global__ __launch_bounds__(kUpSeqBlock) void k_up_seq(UpSeqParams p) {
         if (ri != ~0ull) img[j] = regs[ri * kW + j % kW];
       }
       __syncthreads();
-      const uint64_t kt = ph ? cur.kt_r : cur.kt_e;
+      const uint64_t kt = !kEvents && ph ? cur.kt_r : cur.kt_e;
       for (uint32_t a = 0; a < nprogs; a++) {
         if (!((phase_mask >> a) & 1)) continue;
-        const bool run = ((app >> a) & 1) != 0;
+        const bool run = (!kEvents || need) && ((app >> a) & 1) != 0;
         if (__ballot(run) == 0) continue;
         const UpSeqProg *sp = &p.progs[a];
         const uint32_t kind = __builtin_amdgcn_readfirstlane((uint32_t)sp->kind);
@@ -2028,7 +2051,12 @@ extern "C" hipError_t bpftime_amd_launch_sys_seq(const SeqParams *p, hipStream_t
 extern "C" hipError_t bpftime_amd_launch_up_seq(const UpSeqParams *p, hipStream_t stream) {
   const uint64_t grid = (p->nseg + kUpSeqBlock - 1) / kUpSeqBlock;
   if (grid == 0 || grid > 0x7fffffffull || p->nprogs > kSeqMaxProgs) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_up_seq, dim3((uint32_t)grid), dim3(kUpSeqBlock), 0, stream, *p);
+  if (p->events) {
+    if (!p->perm) return hipErrorInvalidValue;  // (the walk reads its words from it)
+    hipLaunchKernelGGL(k_up_seq<true>, dim3((uint32_t)grid), dim3(kUpSeqBlock), 0, stream, *p);
+  } else {
+    hipLaunchKernelGGL(k_up_seq<false>, dim3((uint32_t)grid), dim3(kUpSeqBlock), 0, stream, *p);
+  }
   return hipGetLastError();
 }
 

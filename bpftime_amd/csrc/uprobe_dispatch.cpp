@@ -31,6 +31,10 @@
 //    pair is the case (example/tracing/funclatency/funclatency.bpf.c: the
 //    entry probe stores starts[tid], the return probe reads it).  The plan is
 //    opt-in, never taken by itself: the refusal above is pinned behaviour.
+//    With an event list (bpftime_amd_uprobe_dispatch_events) the lanes walk
+//    recorded entries and returns, not whole calls: a nested or recursive
+//    call's return runs after the entries recorded inside it, as frida's
+//    on_enter / on_leave order them on the calling thread.
 // Host-side bookkeeping only; the work is on the device.
 #include <errno.h>
 #include <stdlib.h>
@@ -267,7 +271,7 @@ uint64_t up(uint64_t v) { return (v + 255) & ~255ull; }
 std::mutex g_time_mu;
 struct Times {
   float count_ms = 0, gather_ms = 0;  // (thread-ordered plan: the grouping, the replay kernel)
-  uint64_t rows = 0;                  // (... and the records)
+  uint64_t rows = 0;                  // (... and the records, or the events of an event list)
 } g_times;
 
 // a pair of events around launches on s (no-ops unless `on`)
@@ -393,9 +397,15 @@ int64_t run_one(const Attach &a, bool at_entry, const struct bpftime_amd_call_re
 
 // The thread-ordered plan: group the records by caller, one launch for every
 // attachment (vm_api.cpp useq_dispatch).  >= 0 failed callbacks (SYNC), -1 error.
+// With `events` (n_events words (record << 1) | phase) the walked items are the
+// events: they are grouped by their record's caller (uprobe_dispatch.hip
+// k_ug_event_keys, which also counts the events naming no record; the count
+// is read in the grouping's host wait) and the grouping's perm is rewritten to
+// the event words.  One thread walks the caller's list itself.
 int64_t dispatch_threads(const std::vector<Attach> &order, size_t nentry, const struct bpftime_amd_call_records *r,
-                         uint32_t *out_state, int64_t *out_rets, uint32_t flags, StreamBufs &sb, hipStream_t s) {
-  const uint64_t n = r->count;
+                         const uint32_t *events, uint64_t n_events, uint32_t *out_state, int64_t *out_rets,
+                         uint32_t flags, StreamBufs &sb, hipStream_t s) {
+  const uint64_t n = events ? n_events : r->count;  // the walked items
   std::vector<USeqAttach> progs;
   for (size_t i = 0; i < order.size(); i++) {
     const int k = order[i].kind;
@@ -407,16 +417,50 @@ int64_t dispatch_threads(const std::vector<Attach> &order, size_t nentry, const 
   const bool one = (flags & EBPF_BATCH_ORDERED) || !r->pid_tgid;
   const uint64_t gbytes = one ? 0 : bpftime_amd_group_scratch_bytes(n);
   if (!one && !gbytes) return fail("thread grouping of " + std::to_string(n) + " records", EINVAL);
-  uint8_t *buf = grow(sb.group, 256 + gbytes, s);
+  // the failure counter and the out-of-range count | the grouping | the events' keys
+  const uint64_t keys_b = events && !one ? up(8 * n) : 0;
+  uint8_t *buf = grow(sb.group, 256 + up(gbytes) + keys_b, s);
   if (!buf) return fail("scratch allocation failed", ENOMEM);
   const bool timed = (flags & EBPF_BATCH_TIMED) != 0;
   UpSeqParams p{};
   p.nseg = 1;
   Span t_group(timed, s);
+  const void *keys = r->pid_tgid;
+  uint32_t bad = 0;  // (events naming no record: read in the wait below)
+  if (events) {
+    uint32_t *bad_d = (uint32_t *)(buf + 128);
+    keys = one ? nullptr : buf + 256 + up(gbytes);
+    hipError_t e = bpftime_amd_launch_ug_event_keys(events, n, one ? nullptr : r->pid_tgid, r->count, (uint64_t *)keys,
+                                                    bad_d, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, bad_d, 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && one) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+      hipStreamSynchronize(s);  // (nothing is left writing `bad`)
+      return fail(std::string("event key pass: ") + hipGetErrorString(e), EIO);
+    }
+  }
   if (!one) {
-    const hipError_t e = bpftime_amd_group_threads(r->pid_tgid, 8, n, buf + 256, const_cast<uint32_t **>(&p.perm),
+    const hipError_t e = bpftime_amd_group_threads(keys, 8, n, buf + 256, const_cast<uint32_t **>(&p.perm),
                                                    const_cast<uint32_t **>(&p.seg), &p.nseg, s);
-    if (e != hipSuccess) return fail(std::string("thread grouping: ") + hipGetErrorString(e), EIO);
+    if (e != hipSuccess) {
+      hipStreamSynchronize(s);
+      return fail(std::string("thread grouping: ") + hipGetErrorString(e), EIO);
+    }
+  }
+  if (events) {
+    if (bad)
+      return fail(std::to_string(bad) + " of the " + std::to_string(n) + " events name a record index >= count (" +
+                      std::to_string(r->count) + "): nothing was run",
+                  EINVAL);
+    if (order.empty()) return 0;
+    if (one) {
+      p.perm = events;
+    } else {
+      const hipError_t e = bpftime_amd_launch_ug_event_words(const_cast<uint32_t *>(p.perm), events, n, s);
+      if (e != hipSuccess) return fail(std::string("event words: ") + hipGetErrorString(e), EIO);
+    }
+    p.events = 1;
+    p.nrec = r->count;
   }
   t_group.end();
   p.n = n;
@@ -437,6 +481,57 @@ int64_t dispatch_threads(const std::vector<Attach> &order, size_t nentry, const 
     g_times.rows = n;
   }
   return rc;
+}
+
+// What bpftime_amd_uprobe_dispatch and _dispatch_events (`events` non-null:
+// its own refusals made, the flags naming the thread-ordered plan) share: the
+// records' checks, the running attachments, the plan and the stream's buffers
+int64_t dispatch(const struct bpftime_amd_call_records *r, const uint32_t *events, uint64_t n_events,
+                 uint32_t *out_state, int64_t *out_rets, uint32_t flags, void *stream) {
+  if (!r) return fail("no records", EINVAL);
+  if (r->count && !r->func) return fail("no func array: the records need each call's function address", EINVAL);
+  if (r->count > 0xffffffffull) return fail("more than 2^32 records", EINVAL);
+  for (const void *a : {r->enter, r->leave, (const void *)r->func, (const void *)r->pid_tgid, r->clock})
+    if ((uintptr_t)a % 8) return fail("the record arrays must be 8-aligned", EINVAL);
+  std::vector<Attach> entry, leave;
+  running(entry, leave);
+  if (!entry.empty() && r->count && !r->enter)
+    return fail("uprobe / override programs are attached: the records need the enter registers", EINVAL);
+  if (!leave.empty() && r->count && !r->leave)
+    return fail("uretprobe programs are attached: the records need the leave registers", EINVAL);
+  const std::string sbad = stack_fields_bad(r);
+  if (!sbad.empty()) return fail(sbad, EINVAL);
+  bool any_ovr = false;
+  for (const Attach &a : entry) any_ovr |= overrides(a.kind);
+  if (any_ovr && (!out_state || !out_rets))
+    return fail("override / replace programs are attached: out_state and out_rets are needed", EINVAL);
+  std::vector<Attach> order = entry;
+  order.insert(order.end(), leave.begin(), leave.end());
+  const int plan = plan_for(order, flags);
+  if (plan < 0) return -1;
+  // (an event list is range-checked whatever is attached: dispatch_threads)
+  if (!events && (r->count == 0 || order.empty())) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  StreamBufs *sb;
+  std::shared_ptr<std::mutex> mu;
+  {
+    std::lock_guard<std::mutex> g(g_buf_mu);
+    sb = &g_bufs[s];  // (std::map: the node stays where it is)
+    mu = sb->mu;
+  }
+  std::lock_guard<std::mutex> hold(*mu);
+  if (flags & EBPF_BATCH_TIMED) {
+    std::lock_guard<std::mutex> tg(g_time_mu);
+    g_times = Times();
+  }
+  if (plan) return dispatch_threads(order, entry.size(), r, events, n_events, out_state, out_rets, flags, *sb, s);
+  int64_t failed = 0;
+  for (size_t i = 0; i < order.size(); i++) {
+    const int64_t rc = run_one(order[i], i < entry.size(), r, out_state, out_rets, flags, *sb, s);
+    if (rc < 0) return -1;
+    failed += rc;
+  }
+  return failed;
 }
 
 }  // namespace
@@ -538,49 +633,27 @@ int bpftime_amd_uprobe_dispatch_plan(uint32_t flags) {
 
 int64_t bpftime_amd_uprobe_dispatch(const struct bpftime_amd_call_records *r, uint32_t *out_state, int64_t *out_rets,
                                     uint32_t flags, void *stream) {
+  return dispatch(r, nullptr, 0, out_state, out_rets, flags, stream);
+}
+
+int64_t bpftime_amd_uprobe_dispatch_events(const struct bpftime_amd_call_records *r, const uint32_t *events,
+                                           uint64_t n_events, uint32_t *out_state, int64_t *out_rets, uint32_t flags,
+                                           void *stream) {
   if (!r) return fail("no records", EINVAL);
-  if (r->count && !r->func) return fail("no func array: the records need each call's function address", EINVAL);
-  if (r->count > 0xffffffffull) return fail("more than 2^32 records", EINVAL);
-  for (const void *a : {r->enter, r->leave, (const void *)r->func, (const void *)r->pid_tgid, r->clock})
-    if ((uintptr_t)a % 8) return fail("the record arrays must be 8-aligned", EINVAL);
-  std::vector<Attach> entry, leave;
-  running(entry, leave);
-  if (!entry.empty() && r->count && !r->enter)
-    return fail("uprobe / override programs are attached: the records need the enter registers", EINVAL);
-  if (!leave.empty() && r->count && !r->leave)
-    return fail("uretprobe programs are attached: the records need the leave registers", EINVAL);
-  const std::string sbad = stack_fields_bad(r);
-  if (!sbad.empty()) return fail(sbad, EINVAL);
-  bool any_ovr = false;
-  for (const Attach &a : entry) any_ovr |= overrides(a.kind);
-  if (any_ovr && (!out_state || !out_rets))
-    return fail("override / replace programs are attached: out_state and out_rets are needed", EINVAL);
-  std::vector<Attach> order = entry;
-  order.insert(order.end(), leave.begin(), leave.end());
-  const int plan = plan_for(order, flags);
-  if (plan < 0) return -1;
-  if (r->count == 0 || order.empty()) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  StreamBufs *sb;
-  std::shared_ptr<std::mutex> mu;
-  {
-    std::lock_guard<std::mutex> g(g_buf_mu);
-    sb = &g_bufs[s];  // (std::map: the node stays where it is)
-    mu = sb->mu;
-  }
-  std::lock_guard<std::mutex> hold(*mu);
-  if (flags & EBPF_BATCH_TIMED) {
-    std::lock_guard<std::mutex> tg(g_time_mu);
-    g_times = Times();
-  }
-  if (plan) return dispatch_threads(order, entry.size(), r, out_state, out_rets, flags, *sb, s);
-  int64_t failed = 0;
-  for (size_t i = 0; i < order.size(); i++) {
-    const int64_t rc = run_one(order[i], i < entry.size(), r, out_state, out_rets, flags, *sb, s);
-    if (rc < 0) return -1;
-    failed += rc;
-  }
-  return failed;
+  if (!events || !n_events) return fail("no events: the event list needs at least one (record, phase) word", EINVAL);
+  if ((uintptr_t)events % 4) return fail("the event list must be 4-aligned", EINVAL);
+  if (r->count >= (1ull << 31))
+    return fail("2^31 or more records: an event word holds a 31-bit record index", EINVAL);
+  if (n_events > 0xffffffffull) return fail("more than 2^32 - 1 events", EINVAL);
+  // the plan: thread-ordered only
+  if (!(flags & BPFTIME_AMD_DISPATCH_THREADS))
+    return fail("an event list runs under the thread-ordered plan only: BPFTIME_AMD_DISPATCH_THREADS is required",
+                EINVAL);
+  if (flags & BPFTIME_AMD_DISPATCH_PROGRAMS)
+    return fail("BPFTIME_AMD_DISPATCH_PROGRAMS: an event list runs under the thread-ordered plan only "
+                "(BPFTIME_AMD_DISPATCH_THREADS alone)",
+                EINVAL);
+  return dispatch(r, events, n_events, out_state, out_rets, flags, stream);
 }
 
 }  // extern "C"

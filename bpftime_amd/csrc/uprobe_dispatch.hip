@@ -21,6 +21,9 @@
 // record copying its 24 words, strides neighbouring lanes 168 B apart on the
 // load side and 192 B on the store side: every wave access would touch 64
 // different lines for 8 useful bytes each.
+//
+// The thread-ordered plan gathers nothing; its event-list form has two small
+// passes here, k_ug_event_keys and k_ug_event_words (notes beside them).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -140,6 +143,37 @@ __global__ void k_ug_scatter(const uint64_t *rows, uint64_t m, uint64_t n, const
   }
 }
 
+// The event list's key pass (bpftime_amd_uprobe_dispatch_events): lane e reads
+// events[e] (4 B per lane, contiguous) and writes the thread of its record,
+// keys[e] = pid[events[e] >> 1] (8 B per lane, contiguous; the pid load is the
+// one gather).  An event whose record is not below nrec gets key 0, is never
+// dereferenced and is counted: one ballot per wave, one atomic add per wave
+// that saw any.  Null keys: the range check alone (one thread walks the list).
+__global__ __launch_bounds__(kUgBlock) void k_ug_event_keys(const uint32_t *events, uint64_t n, const uint64_t *pid,
+                                                            uint64_t nrec, uint64_t *keys, uint32_t *bad) {
+  const uint32_t lane = threadIdx.x & 63;
+  uint32_t mine = 0;  // (wave-uniform)
+  // (whole waves take the loop together: the bound is rounded up to 64)
+  const uint64_t n64 = (n + 63) & ~63ull;
+  for (uint64_t e = (uint64_t)blockIdx.x * kUgBlock + threadIdx.x; e < n64; e += (uint64_t)gridDim.x * kUgBlock) {
+    const bool in = e < n;
+    const uint64_t rec = in ? events[e] >> 1 : 0;
+    const bool out = in && rec >= nrec;
+    if (in && keys) keys[e] = out ? 0 : pid[rec];
+    mine += (uint32_t)__popcll(__ballot(out));
+  }
+  if (lane == 0 && mine) atomicAdd(bad, mine);
+}
+
+// After the grouping: perm[k], an index into the event list, becomes the event
+// word itself, so each step of the walk has one dependent load fewer
+__global__ __launch_bounds__(kUgBlock) void k_ug_event_words(uint32_t *perm, const uint32_t *events, uint64_t n) {
+  for (uint64_t k = (uint64_t)blockIdx.x * kUgBlock + threadIdx.x; k < n; k += (uint64_t)gridDim.x * kUgBlock) {
+    const uint32_t e = perm[k];
+    if (e < n) perm[k] = events[e];
+  }
+}
+
 static uint32_t wave_grid(uint32_t chunks) {
   const uint32_t blocks = (chunks + kUgBlock / 64 - 1) / (kUgBlock / 64);
   return blocks > 4096 ? 4096 : blocks ? blocks : 1;
@@ -159,6 +193,28 @@ extern "C" hipError_t bpftime_amd_launch_ug_count(const UGather *g, hipStream_t 
 
 extern "C" hipError_t bpftime_amd_launch_ug_gather(const UGather *g, hipStream_t stream) {
   hipLaunchKernelGGL(k_ug_gather, dim3(wave_grid(g->chunks)), dim3(kUgBlock), 0, stream, *g);
+  return hipGetLastError();
+}
+
+static uint32_t lane_grid(uint64_t n) {
+  const uint64_t blocks = (n + kUgBlock - 1) / kUgBlock;
+  return blocks > 4096 ? 4096 : blocks ? (uint32_t)blocks : 1;
+}
+
+extern "C" hipError_t bpftime_amd_launch_ug_event_keys(const uint32_t *events, uint64_t n, const uint64_t *pid,
+                                                       uint64_t nrec, uint64_t *keys, uint32_t *bad,
+                                                       hipStream_t stream) {
+  if (!events || !n || !bad || (keys && !pid)) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(bad, 0, 4, stream);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_ug_event_keys, dim3(lane_grid(n)), dim3(kUgBlock), 0, stream, events, n, pid, nrec, keys, bad);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t bpftime_amd_launch_ug_event_words(uint32_t *perm, const uint32_t *events, uint64_t n,
+                                                        hipStream_t stream) {
+  if (!perm || !events || !n) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_ug_event_words, dim3(lane_grid(n)), dim3(kUgBlock), 0, stream, perm, events, n);
   return hipGetLastError();
 }
 

@@ -53,4 +53,13 @@ hipError_t bpftime_amd_launch_ug_gather(const bpftime_amd::UGather *g, hipStream
 hipError_t bpftime_amd_launch_ug_scatter(const uint64_t *rows, uint64_t m, uint64_t n, const uint32_t *state,
                                          const int64_t *vals, int replace, uint32_t *out_state, int64_t *out_rets,
                                          hipStream_t stream);
+// The event list (bpftime_amd_uprobe_dispatch_events), n words (record << 1) |
+// phase.  _event_keys: keys[e] = pid[record of events[e]] for the thread
+// grouping (null keys: none are written) and *bad = the events whose record is
+// not below nrec (zeroed here; such an event gets key 0 and is not
+// dereferenced).  _event_words: the grouping's perm, indexes into the list,
+// rewritten in place to the event words
+hipError_t bpftime_amd_launch_ug_event_keys(const uint32_t *events, uint64_t n, const uint64_t *pid, uint64_t nrec,
+                                            uint64_t *keys, uint32_t *bad, hipStream_t stream);
+hipError_t bpftime_amd_launch_ug_event_words(uint32_t *perm, const uint32_t *events, uint64_t n, hipStream_t stream);
 }

@@ -597,6 +597,32 @@ def uprobe_dispatch(func: Optional[DeviceBuffer], n: int, enter: Optional[Device
     return rc
 
 
+def call_event(record: int, phase: int) -> int:
+    """BPFTIME_AMD_CALL_EVENT: the event word of a record's entry (phase 0) or
+    return (phase 1)."""
+    return ((record << 1) | (phase & 1)) & 0xFFFFFFFF
+
+
+def uprobe_dispatch_events(func: Optional[DeviceBuffer], n: int, events: Optional[DeviceBuffer], n_events: int,
+                           enter: Optional[DeviceBuffer] = None, leave: Optional[DeviceBuffer] = None,
+                           pid_tgid: Optional[DeviceBuffer] = None, clock: Optional[DeviceBuffer] = None,
+                           out_state: Optional[DeviceBuffer] = None, out_rets: Optional[DeviceBuffer] = None,
+                           flags: int = BATCH_SYNC | DISPATCH_THREADS, stream: int = 0) -> int:
+    """The thread-ordered uprobe replay over an event list
+    (bpftime_amd_uprobe_dispatch_events): n records as uprobe_dispatch's, and
+    n_events u32 words call_event(record, phase) in recorded order, so nested
+    and recursive calls run entry, inner entry, inner return, return.  flags
+    must carry DISPATCH_THREADS (| BATCH_ORDERED: one lane, the serial run).
+    Returns the failed callbacks (BATCH_SYNC)."""
+    p = lambda b: b.ptr if b else None  # noqa: E731
+    r = CallRecords(enter=p(enter), leave=p(leave), func=p(func), pid_tgid=p(pid_tgid), clock=p(clock), count=n)
+    rc = lib().bpftime_amd_uprobe_dispatch_events(C.byref(r), p(events), n_events, p(out_state), p(out_rets), flags,
+                                                  stream or None)
+    if rc < 0:
+        raise EbpfError(f"uprobe dispatch failed: {_err()}")
+    return rc
+
+
 def uprobe_dispatch_plan(flags: int = 0) -> int:
     """1 when a uprobe dispatch with these flags runs thread-ordered for the
     current attachments, 0 program-major; raises with the named error such a

@@ -625,8 +625,9 @@ struct bpftime_amd_call_records {
  * order; per call the entry callbacks of its function run in attach order,
  * then its return callbacks (frida_internal_attach_entry.cpp:221-239), which
  * attachments run at a function decided as above.  Threads are unordered
- * against each other, as in the reference; a call's return never follows
- * another call's entry (no nesting).  Every callback gets a fresh copy of the
+ * against each other, as in the reference; here a record's return runs right
+ * after its entry -- calls recorded inside one another take the event list
+ * (bpftime_amd_uprobe_dispatch_events below).  Every callback gets a fresh copy of the
  * phase's pt_regs, the record's caller and clock[i][phase], its attachment's
  * func_ip / cookie and its VM's task identity; counter adds reach memory at
  * once, so a thread's later callback sees its earlier one; out_state /
@@ -650,6 +651,54 @@ struct bpftime_amd_call_records {
  * attachment without out_state / out_rets. */
 int64_t bpftime_amd_uprobe_dispatch(const struct bpftime_amd_call_records *r, uint32_t *out_state,
                                     int64_t *out_rets, uint32_t flags, void *stream);
+/* Nested and recursive calls: the thread-ordered plan over an event list.
+ * frida's listener runs a function's uprobes in on_enter and its uretprobes in
+ * on_leave, on the calling thread, when each happens
+ * (frida_internal_attach_entry.cpp:221-239): with f and g probed and f calling
+ * g the order is f entry, g entry, g return, f return.  `events` is a device
+ * array of n_events words in recorded order, all threads interleaved; a word
+ * names a record and a phase.  `r` is the record struct above, unchanged: a
+ * record still holds both register sets, func, pid_tgid and clock[i] = {entry
+ * ns, return ns}.
+ *  - Plan: thread-ordered only.  `flags` must carry
+ *    BPFTIME_AMD_DISPATCH_THREADS; EBPF_BATCH_ORDERED may be added (one lane
+ *    walks the whole list in list order: the serial reference run); without the
+ *    flag, or with BPFTIME_AMD_DISPATCH_PROGRAMS, -1 + EINVAL, the error naming
+ *    the flag.  bpftime_amd_uprobe_dispatch_plan answers for these flags.
+ *  - An event belongs to thread pid_tgid[record] (NULL: one thread owns every
+ *    event); both phases of a call run on the calling thread.  Lane t walks
+ *    thread t's events in list order; threads are unordered against each other.
+ *  - Per event: phase 0 runs the entry callbacks of func[record], phase 1 its
+ *    return callbacks -- which attachments, and in which order, as above (a
+ *    function hooked by replacement runs its override / replace at phase 0 and
+ *    nothing at phase 1).  Every callback gets a fresh copy of enter[record] /
+ *    leave[record] with r2 = 168, clock[record][phase] (NULL: the device
+ *    clock), the record's caller, its attachment's func_ip / cookie and its
+ *    VM's identity; 58 / 187 and a replace's r0 write out_state[record] /
+ *    out_rets[record] as above; counter adds reach memory at once.
+ *  - No pairing is required or checked: the replay runs what the list says.  A
+ *    record may appear with its entry only (a call that never returned), with
+ *    its return only (entered before recording began) or not at all -- then
+ *    nothing runs for it and its out_* entries keep the caller's values; the
+ *    same event twice runs twice.
+ *  - The flat list E(0,0), E(0,1), E(1,0), E(1,1), ... gives exactly what
+ *    bpftime_amd_uprobe_dispatch with BPFTIME_AMD_DISPATCH_THREADS gives on the
+ *    same records.
+ * Refused with -1 and a named error, before any callback runs and with no map
+ * changed: `events` NULL or n_events 0; count >= 2^31 (a word holds a 31-bit
+ * record index); n_events >= 2^32; an event whose record index is >= count
+ * (counted on the device and read in the host's one wait, the grouping's --
+ * with one thread, a wait of its own; the error tells how many); and every
+ * refusal of the thread-ordered plan and of the record checks above.
+ * The return value and EBPF_BATCH_SYNC / _UNCHECKED / _TIMED as the
+ * thread-ordered dispatch's; after a timed call bpftime_amd_uprobe_last_ms
+ * tells the grouping's time (the key pass included), the replay launch's, and
+ * n_events as the rows. */
+#define BPFTIME_AMD_CALL_EVENT(record, phase) (((uint32_t)(record) << 1) | ((uint32_t)(phase) & 1u))
+int64_t bpftime_amd_uprobe_dispatch_events(const struct bpftime_amd_call_records *r,
+                                           const uint32_t *events, uint64_t n_events,
+                                           uint32_t *out_state, int64_t *out_rets,
+                                           uint32_t flags, void *stream);
 /* The plan a dispatch with these flags takes for the current attachments: 1
  * thread-ordered, 0 program-major, -1 with the named error such a dispatch
  * would give (both plan flags, a pair that may not commute, a thread-ordered
