@@ -172,6 +172,7 @@ SIGNATURES = [
     ("bpftime_amd_uprobe_dispatch_events", C.c_int64, [C.POINTER(CallRecords), C.c_void_p, C.c_uint64, C.c_void_p,
                                                        C.c_void_p, C.c_uint32, C.c_void_p]),
     ("bpftime_amd_uprobe_dispatch_plan", C.c_int, [C.c_uint32]),
+    ("bpftime_amd_last_seq_tier", C.c_int, []),
     ("bpftime_amd_uprobe_last_ms", C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), u64p]),
     ("bpftime_amd_enable_trace_printk", C.c_int, [C.c_int]),
     ("bpftime_amd_trace_read", C.c_int64, [C.POINTER(TraceLine), C.c_uint64, C.c_void_p, C.c_uint64, u64p]),

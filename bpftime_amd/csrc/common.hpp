@@ -547,11 +547,18 @@ static_assert(sizeof(SeqProg) == 32, "SeqProg is read with scalar loads");
 constexpr uint32_t kSeqMaxProgs = 64;  // attached programs a thread-ordered dispatch runs (kernel arguments)
 // k_sys_seq's per-lane ctx copy: the 64-B ctx, then the record's caller
 // (pid_tgid) and the clock of the callback's phase, read by the asm tier's
-// CALL_REC handler (loader.cpp link_fast rec_helpers)
+// CALL_REC handler (loader.cpp link_fast rec)
 constexpr uint32_t kSeqPidOff = 64, kSeqClockOff = 72, kSeqCtxWords = 10;
 // threads up to which the thread-ordered dispatch runs its callbacks in the
 // asm tier (vm_api.cpp seq_dispatch)
 constexpr uint64_t kSeqAsmThreads = 16384;
+// Where a thread-ordered kernel keeps a callback's caller and clock, as byte
+// offsets from the lane's ctx copy (loader.cpp link_fast: the CALL_REC links'
+// aux; pid 0: no such links)
+struct RecOffs {
+  uint32_t pid = 0, clock = 0;
+};
+constexpr RecOffs kSeqRecOffs{kSeqPidOff, kSeqClockOff};
 struct SeqParams {
   uint32_t nprogs;
   // the records' fields (include/bpftime_amd.h: 64- / 96- / 128-B records or
@@ -611,6 +618,15 @@ static_assert(sizeof(UpSeqProg) == 40, "UpSeqProg is read with scalar loads");
 // barriers, and waves of one block would leave their ragged walks at different
 // records (Uprobe replay)
 constexpr uint32_t kUpSeqBlock = 64;
+// k_up_seq's per-lane ctx copy: the 168-B pt_regs, then the callback's caller
+// and the clock of its phase (CALL_REC, as kSeqPidOff / kSeqClockOff; the
+// program-major rows keep the two at the same offsets)
+constexpr uint32_t kUpSeqPidOff = 168, kUpSeqClockOff = 176, kUpSeqCtxWords = 23;
+constexpr RecOffs kUpSeqRecOffs{kUpSeqPidOff, kUpSeqClockOff};
+// threads up to which the thread-ordered uprobe replay runs its callbacks in
+// the asm tier (vm_api.cpp useq_dispatch): the largest count measured, where
+// the asm tier still led (profiles/uprobe_asm_measurement.txt)
+constexpr uint64_t kUpSeqAsmThreads = 65536;
 struct UpSeqParams {
   uint32_t nprogs;
   uint32_t exact;         // one lane over every record (EBPF_BATCH_ORDERED)
@@ -646,7 +662,10 @@ struct UpSeqParams {
   // words, or the caller's list itself for one thread) and nrec is the record
   // count: a word whose record is not below it runs nothing
   uint32_t events;
-  uint32_t pad;
+  // 1: every program keeps its stack within kLdsStackMax bytes: the stacks
+  // live in LDS and the callbacks run in the asm tier (seq_lds_bytes); 0:
+  // private stacks, the C++ tier only
+  uint32_t fast;
   uint64_t nrec;
 };
 static_assert(sizeof(UpSeqParams) <= 4096, "kernel arguments");

@@ -1766,9 +1766,15 @@ extern "C" int bpftime_amd_seq_prof(unsigned long long *out, int reset) {
 // the 64 x 21-word image, so a wave load covers 512 contiguous image bytes
 // made of whole runs of one record's consecutive words (a lane-per-record copy
 // would put neighbouring lanes 168 B apart); each callback then copies its
-// lane's 21 words from the image inside LDS.  The callbacks run in the C++
-// tier (run_loop, private 512-B stacks) with the ORDERED links, as k_sys_seq's
-// C++ tier does; there is no asm tier here.
+// lane's 21 words from the image inside LDS.  The callbacks run with the
+// ORDERED links in the C++ tier (run_loop, private 512-B stacks) or (p.fast)
+// in the asm tier with k_sys_seq's per-callback loop: the lanes' stacks are
+// kLdsStackMax bytes of dynamic LDS each, the caller and the phase's clock sit
+// behind the ctx copy for CALL_REC (common.hpp kUpSeqPidOff / kUpSeqClockOff),
+// and every instruction the asm leaves -- 58 / 187 and the map helpers among
+// them -- takes the same C++ step and helper path either way.  (173 / 174: the
+// loader marks their callers for the scratch-stack kernels, and the host keeps
+// a dispatch with such a program in the C++ tier, vm_api.cpp useq_dispatch.)
 //
 // kEvents (bpftime_amd_uprobe_dispatch_events): the walked words are events,
 // (record << 1) | phase, in the thread's recorded order, so a nested or
@@ -1783,13 +1789,43 @@ __global__ __launch_bounds__(kUpSeqBlock) void k_up_seq(UpSeqParams p) {
   // r0..r10 columns and the dummy slot, at run_loop's column stride (kBlock)
   __shared__ uint64_t Rf[11 * kBlock + kUpSeqBlock];
   __shared__ uint64_t img[kW * kUpSeqBlock];  // the staged records of the phase: [lane][21]
-  __shared__ uint64_t cx[kW * kUpSeqBlock];   // the running callback's ctx copy: [lane][21]
+  // the running callback's ctx copy, its caller and clock: [lane][21 + 2]
+  __shared__ uint64_t cx[kUpSeqCtxWords * kUpSeqBlock];
   __shared__ uint64_t srec[kUpSeqBlock];      // the lanes' record indexes for the staging (all ones: none)
   const uint32_t tid = threadIdx.x;
   const uint64_t t = (uint64_t)blockIdx.x * kUpSeqBlock + tid;
+  // the callbacks' stacks and the asm's launch constants, as k_sys_seq's
+  // (common.hpp seq_lds_bytes)
+  extern __shared__ __attribute__((aligned(16))) uint8_t dyn[];
+  const bool fast = __builtin_amdgcn_readfirstlane(p.fast) != 0;
   uint64_t stk[kStackSize / 8];
-  const uint64_t stack_top = (uint64_t)(uintptr_t)(stk + kStackSize / 8);
-  uint64_t *const ctx = &cx[kW * tid];
+  const uint64_t stack_top = fast ? (uint64_t)(uintptr_t)(dyn + (tid + 1) * kLdsStackMax)
+                                  : (uint64_t)(uintptr_t)(stk + kStackSize / 8);
+  const uint32_t sbytes = fast ? kLdsStackMax : kStackSize;
+  uint64_t *const ctx = &cx[kUpSeqCtxWords * tid];
+  FastEnv fe{};
+  if (fast) {
+    // (tenv all zero, no combining table: k_sys_seq)
+    uint64_t *const tenv = (uint64_t *)(dyn + kUpSeqBlock * kLdsStackMax);
+    for (uint32_t i = tid; i < kTenvBytes / 8; i += kUpSeqBlock) tenv[i] = 0;
+    fe.maps = p.maps;
+    fe.comb = sreg((uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(tenv + kTenvBytes / 8)));
+    fe.combn = 0;
+    fe.head = 0;
+    fe.oflags = 0;  // callbacks' return values are not stored (a replace: below)
+    fe.dlo = sreg((uint64_t)0);
+    const uint32_t dh = __builtin_amdgcn_readfirstlane(p.checked ? 0u : ~0u);
+    fe.dhi = sreg(((uint64_t)dh << 32) | dh);
+    fe.alo = p.arena_lo;
+    fe.ahi = p.arena_hi;
+    fe.shi = sreg((uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)(uintptr_t)&Rf[0] >> 32)));
+    fe.phi = fe.shi;
+    fe.rb = (uint32_t)(uintptr_t)&Rf[0] + 8 * tid;
+    fe.stage = 0;
+    fe.ncpu = p.ncpu ? p.ncpu : 1;
+    fe.sstep = fe.ustep = 0;
+  }
+  __syncthreads();
   Ctx c;
   c.R = &Rf[tid];
   // the programs see their ctx copy (LDS), their stack and the map arena
@@ -1879,8 +1915,14 @@ __global__ __launch_bounds__(kUpSeqBlock) void k_up_seq(UpSeqParams p) {
         const uint32_t kind = __builtin_amdgcn_readfirstlane((uint32_t)sp->kind);
         // each callback on its own copy of the registers: stores through r1
         // reach neither the records nor the next callback
-        if (run)
+        if (run) {
           for (uint32_t w = 0; w < kW; w++) ctx[w] = img[kW * tid + w];
+          // the asm tier's bpf_get_current_pid_tgid / bpf_ktime_get_ns (CALL_REC)
+          if (fast) {
+            ctx[kUpSeqPidOff / 8] = pid;
+            ctx[kUpSeqClockOff / 8] = clk ? kt : (uint64_t)__builtin_amdgcn_s_memrealtime() * 10ull;
+          }
+        }
         c.prog = (prog_ptr)rfl64((uint64_t)(uintptr_t)sp->prog);
         c.fast = (const FInsn *)rfl64((uint64_t)(uintptr_t)sp->fast);
         for (int r = 0; r <= 10; r++) c.R[r * kBlock] = 0;
@@ -1897,8 +1939,46 @@ __global__ __launch_bounds__(kUpSeqBlock) void k_up_seq(UpSeqParams p) {
         uint64_t miss_hash = 0;
         uint32_t lru_ops = 0;
         bool uni = true;
+        // the asm tier's view of the callback (k_sys_seq): a fresh entry on the
+        // lane's ctx copy and LDS stack, the running lanes as c.alive has them
+        // (kEvents: the lanes of this phase alone)
+        FastUnit fu{};
+        if (fast) {
+          fe.fast = c.fast;
+          fu.r1 = fu.slot = (uint64_t)(uintptr_t)ctx;
+          fu.r2 = fu.len = kPtRegsBytes;
+          fu.r10 = stack_top;
+          fu.entry = 1u | 4u;  // fresh, lane groups scheduled in asm
+          fu.vm = (uint32_t)((idx / 64) % fe.ncpu);
+        }
+        // a replace returns its r0, which the asm's exit leaves in no LDS
+        // column: its callback runs in the C++ loops, on the LDS stack
+        const bool fast_cb = fast && kind != kUpReplace;
         while (__ballot(c.alive) != 0) {
-          const uint32_t r = uni ? run_loop<true>(c) : run_loop<false>(c);
+          uint32_t r;
+          if (fast_cb && uni) {
+            uint32_t adv = 0;
+            fu.entry = (fu.entry & ~256u) | (__ballot(miss_fd >= 0) != 0 ? 256u : 0u);  // (k_interp)
+            const uint32_t why = run_fast<false>(c, fe, fu, 0u, adv);
+            fu.entry &= ~1u;  // re-entries read the registers from their LDS columns
+            if (why == FAST_EXIT) {  // every running lane ran exit
+              c.alive = false;
+              break;
+            }
+            if (why == FAST_SPLIT) {  // lane groups at different pcs (c.lpc): the C++ divergent loop
+              uni = false;
+              continue;
+            }
+            if (why == FAST_STEPS) {
+              c.err = c.alive ? E_STEPS : c.err;
+              c.alive = false;
+              break;
+            }
+            r = run_loop<true, true>(c);  // the instruction the asm does not run
+          } else {
+            r = uni ? run_loop<true>(c) : run_loop<false>(c);
+          }
+          if (r == R_STEP) continue;
           if (r == R_DONE) break;
           if (r == R_DIVERGE) {
             uni = false;
@@ -1933,7 +2013,7 @@ __global__ __launch_bounds__(kUpSeqBlock) void k_up_seq(UpSeqParams p) {
             env.ktime = kt;
             uint32_t cerr = E_OK;
             uint64_t *R = c.R;
-            const MemLane ml{stack_top - kStackSize, (uint64_t)(uintptr_t)ctx, kStackSize, kPtRegsBytes};
+            const MemLane ml{stack_top - sbytes, (uint64_t)(uintptr_t)ctx, sbytes, kPtRegsBytes};
             // the attached program's VM's identity and the attachment's own
             // func_ip / cookie (no recorded stacks: the host refuses 27 / 67)
             TaskEnv te{};
@@ -2051,11 +2131,12 @@ extern "C" hipError_t bpftime_amd_launch_sys_seq(const SeqParams *p, hipStream_t
 extern "C" hipError_t bpftime_amd_launch_up_seq(const UpSeqParams *p, hipStream_t stream) {
   const uint64_t grid = (p->nseg + kUpSeqBlock - 1) / kUpSeqBlock;
   if (grid == 0 || grid > 0x7fffffffull || p->nprogs > kSeqMaxProgs) return hipErrorInvalidValue;
+  const size_t lds = seq_lds_bytes(kUpSeqBlock, p->fast != 0);
   if (p->events) {
     if (!p->perm) return hipErrorInvalidValue;  // (the walk reads its words from it)
-    hipLaunchKernelGGL(k_up_seq<true>, dim3((uint32_t)grid), dim3(kUpSeqBlock), 0, stream, *p);
+    hipLaunchKernelGGL(k_up_seq<true>, dim3((uint32_t)grid), dim3(kUpSeqBlock), lds, stream, *p);
   } else {
-    hipLaunchKernelGGL(k_up_seq<false>, dim3((uint32_t)grid), dim3(kUpSeqBlock), 0, stream, *p);
+    hipLaunchKernelGGL(k_up_seq<false>, dim3((uint32_t)grid), dim3(kUpSeqBlock), lds, stream, *p);
   }
   return hipGetLastError();
 }

@@ -2094,16 +2094,17 @@ static void link_staged(const FastForm &f, uint32_t head, uint32_t stage, bool o
 
 void link_fast(const FastForm &f, uint32_t head, uint32_t stage, bool ordered, const std::vector<DInsn> &prog,
                std::vector<FInsn> &out, int32_t unwind_idx, uint32_t lc_sets, uint32_t pid_off, bool no_kldx,
-               bool rec_helpers) {
+               RecOffs rec) {
   link_staged(f, head, stage, ordered, prog, out);
-  // rec_helpers (the thread-ordered kernel): bpf_get_current_pid_tgid and
+  // rec (the thread-ordered kernels): bpf_get_current_pid_tgid and
   // bpf_ktime_get_ns read the caller / clock the kernel keeps beside the
-  // lane's ctx copy (interp.hip k_sys_seq: ctx + kSeqPidOff / kSeqClockOff)
-  if (rec_helpers)
+  // lane's ctx copy (interp.hip k_sys_seq: ctx + kSeqPidOff / kSeqClockOff;
+  // k_up_seq: ctx + kUpSeqPidOff / kUpSeqClockOff)
+  if (rec.pid)
     for (size_t i = 0; i < prog.size() && i < out.size(); i++)
       if (prog[i].op == X_CALL && (prog[i].hi == 14 || prog[i].hi == 5) && unwind_idx != prog[i].hi) {
         out[i].hoff = 4 + 4 * F_CALL_REC;
-        out[i].aux = (int32_t)(prog[i].hi == 14 ? kSeqPidOff : kSeqClockOff);
+        out[i].aux = (int32_t)(prog[i].hi == 14 ? rec.pid : rec.clock);
       }
   // no_kldx: the launch runs other programs that may write the array
   // storage this one reads at constant addresses (the thread-ordered

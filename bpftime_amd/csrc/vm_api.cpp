@@ -351,7 +351,7 @@ struct Image {
   // greg: the asm variant of the launch (k_interp G), whose handler offsets
   // the form is translated to
   const FInsn *linked(bool greg, bool xdp, uint32_t head, uint32_t stage, bool ordered, int32_t unwind_idx,
-                      uint32_t lc_sets, int32_t pid_off, bool no_kldx = false, bool rec_helpers = false) {
+                      uint32_t lc_sets, int32_t pid_off, bool no_kldx = false, RecOffs rec = {}) {
     std::lock_guard<std::mutex> g(link_mu);
     // (the helpers with asm handlers an unwind index changes: lookup, pid_tgid)
     const bool uw = unwind_idx == 1, uwp = unwind_idx == 14;
@@ -360,13 +360,15 @@ struct Image {
                          ((uint64_t)(lc_sets & 0x1fff) << 47) | ((uint64_t)stage << 40) | ((uint64_t)po << 32) |
                          (stage ? head : 0);
     const bool uwu = unwind_idx == 2;  // (map_update_elem's asm handler)
-    const auto lk = std::make_pair(key, (uint32_t)no_kldx | ((uint32_t)rec_helpers << 1) | ((uint32_t)uwu << 2) |
-                                            ((uint32_t)greg << 3));
+    // (rec: the ctx copy's caller / clock offsets, both below 256)
+    const auto lk = std::make_pair(key, (uint32_t)no_kldx | ((uint32_t)(rec.pid != 0) << 1) | ((uint32_t)uwu << 2) |
+                                            ((uint32_t)greg << 3) | ((rec.pid & 0xffu) << 8) |
+                                            ((rec.clock & 0xffu) << 16));
     auto it = links.find(lk);
     if (it != links.end()) return it->second;
     std::vector<FInsn> out;
     link_fast(xdp ? fx : fr, head, stage, ordered, prog.prog, out, uw ? 1 : uwu ? 2 : -1, lc_sets, po, no_kldx,
-              rec_helpers);
+              rec);
     if (getenv("BPFTIME_AMD_DUMP_FAST"))  // the linked threaded form, one FInsn a line
       for (size_t i = 0; i < out.size(); i++)
         fprintf(stderr, "bpftime_amd: fast %3zu %-18s w1 %08x imm %llx dst %u src %u tgt %u aux %x\n", i,
@@ -1566,6 +1568,10 @@ bool vm_touches_qs(const ::ebpf_vm *vm) {
 extern "C" hipError_t bpftime_amd_launch_sys_seq(const SeqParams *p, hipStream_t stream);
 extern "C" hipError_t bpftime_amd_launch_up_seq(const UpSeqParams *p, hipStream_t stream);
 
+// the tier of this host thread's most recent thread-ordered dispatch (1 asm,
+// 0 C++, -1 none yet): bpftime_amd_last_seq_tier
+static thread_local int g_last_seq_tier = -1;
+
 namespace {
 // What the thread-ordered launches (k_sys_seq, k_up_seq) share: per attached
 // program the checks and the upkeep flags exec_batch derives for one launch,
@@ -1611,13 +1617,15 @@ struct SeqLaunch {
   }
 
   // One attached program: its image and ORDERED link, and the index of its
-  // VM's identity in `tasks` (one table entry per distinct identity)
-  bool add(Mi355xVm *vm, bool no_kldx, bool fast, SeqTask *tasks, const DInsn *&prog, const FInsn *&link,
+  // VM's identity in `tasks` (one table entry per distinct identity).  `rec`:
+  // the asm tier's link, with the kernel's caller / clock offsets (pid 0: the
+  // C++ tier's)
+  bool add(Mi355xVm *vm, bool no_kldx, RecOffs rec, SeqTask *tasks, const DInsn *&prog, const FInsn *&link,
            uint32_t &task) {
     auto im = vm->image();
     if (!vm->loaded || !im) return fail("an attached program is not loaded");
     if (vm->has_tail) return fail("an attached program calls bpf_tail_call (program-major dispatch runs it)");
-    link = im->linked(false, false, 0, 0, true, -1, 0, 0, no_kldx, fast);
+    link = im->linked(false, false, 0, 0, true, -1, 0, 0, no_kldx, rec);
     if (!link) return fail("device upload failed");
     prog = im->d_prog;
     SeqTask tk{};
@@ -1757,7 +1765,7 @@ int64_t seq_dispatch(const std::vector<SeqAttach> &progs, const SysLayout &lay, 
   const bool no_kldx = L.array_writes(vms) && progs.size() > 1;
   for (const SeqAttach &a : progs) {
     SeqProg &q = p.progs[p.nprogs++];
-    if (!L.add(a.vm->impl, no_kldx, fast, p.tasks, q.prog, q.fast, q.task)) return fail(L.err);
+    if (!L.add(a.vm->impl, no_kldx, fast ? kSeqRecOffs : RecOffs{}, p.tasks, q.prog, q.fast, q.task)) return fail(L.err);
     q.sys_nr = a.sys_nr;
     q.enter = a.enter ? 1 : 0;
     // its attach cookie (a link's; a syscall tracepoint has no func_ip)
@@ -1787,6 +1795,7 @@ int64_t seq_dispatch(const std::vector<SeqAttach> &progs, const SysLayout &lay, 
   hipError_t e = hipMemsetAsync(err, 0, 4, s);
   if (e == hipSuccess) e = bpftime_amd_launch_sys_seq(&p, s);
   if (e != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(e));
+  g_last_seq_tier = fast ? 1 : 0;
   L.after();
   if (!(flags & EBPF_BATCH_SYNC)) return 0;
   const int64_t failed = L.finish(err, s);
@@ -1810,14 +1819,31 @@ int64_t useq_dispatch(const std::vector<USeqAttach> &progs, const UpSeqParams &r
   UpSeqParams p = recs;  // (the records, their grouping and the outputs: uprobe_dispatch.cpp)
   p.nprogs = 0;
   SeqLaunch L((flags & EBPF_BATCH_ORDERED) != 0);
+  // the tier, by seq_dispatch's rule: the asm tier when every stack fits the
+  // LDS stacks and the threads are at most kUpSeqAsmThreads (measured:
+  // profiles/uprobe_asm_measurement.txt; an ORDERED dispatch is one thread and
+  // so takes the asm tier too); BPFTIME_AMD_SEQ_ASM=1 / 0 forces a tier, and
+  // a forced 1 still falls back when a program does not qualify
+  const char *asm_env = getenv("BPFTIME_AMD_SEQ_ASM");
+  bool fast = asm_env && asm_env[0] ? asm_env[0] != '0' : p.nseg <= kUpSeqAsmThreads;
+  const bool fast_asked = fast;
+  int fallback = -1;  // the first attached program that keeps the dispatch in the C++ tier
   std::vector<const ::ebpf_vm *> vms;
-  for (const USeqAttach &a : progs) vms.push_back(a.vm);
+  for (const USeqAttach &a : progs) {
+    vms.push_back(a.vm);
+    auto im = a.vm->impl->image();
+    if (!im) continue;
+    if (fast && (im->prog.big_stack || im->prog.stack_size > kLdsStackMax)) {
+      fast = false;
+      fallback = (int)vms.size() - 1;
+    }
+  }
   const bool no_kldx = L.array_writes(vms) && progs.size() > 1;
   for (const USeqAttach &a : progs) {
     UpSeqProg &q = p.progs[p.nprogs++];
     uint32_t task = 0;
-    // (the C++ tier only: private stacks, no LDS-stack link)
-    if (!L.add(a.vm->impl, no_kldx, false, p.tasks, q.prog, q.fast, task)) return fail(L.err);
+    if (!L.add(a.vm->impl, no_kldx, fast ? kUpSeqRecOffs : RecOffs{}, p.tasks, q.prog, q.fast, task))
+      return fail(L.err);
     q.task = (uint16_t)task;
     q.func = a.func;
     q.phase = a.at_return ? 1 : 0;
@@ -1837,10 +1863,24 @@ int64_t useq_dispatch(const std::vector<USeqAttach> &progs, const UpSeqParams &r
   p.trace_log = trace_log().d;
   p.trace_cap = trace_log().cap;
   p.exact = L.ordered ? 1 : 0;
+  p.fast = fast ? 1 : 0;
   if (!L.before(p.n, p.lru_seq)) return fail(L.err);
+  if (getenv("BPFTIME_AMD_VERBOSE")) {
+    std::string why;
+    if (fast_asked && !fast)
+      why = " (program " + std::to_string(fallback) + " at func 0x" + [&] {
+        char b[32];
+        snprintf(b, sizeof b, "%llx", (unsigned long long)progs[fallback].func);
+        return std::string(b);
+      }() + " needs a stack of more than " + std::to_string(kLdsStackMax) + " B or the scratch-stack kernels)";
+    fprintf(stderr, "bpftime_amd: launch uprobe replay %s items %llu threads %llu block %u programs %u tier %s%s lds %zu\n",
+            p.events ? "events" : "calls", (unsigned long long)p.n, (unsigned long long)p.nseg, kUpSeqBlock, p.nprogs,
+            fast ? "asm" : "c++", why.c_str(), seq_lds_bytes(kUpSeqBlock, fast));
+  }
   hipError_t e = hipMemsetAsync(err, 0, 4, s);
   if (e == hipSuccess) e = bpftime_amd_launch_up_seq(&p, s);
   if (e != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(e));
+  g_last_seq_tier = fast ? 1 : 0;
   L.after();
   if (!(flags & EBPF_BATCH_SYNC)) return 0;
   const int64_t failed = L.finish(err, s);
@@ -1849,6 +1889,8 @@ int64_t useq_dispatch(const std::vector<USeqAttach> &progs, const UpSeqParams &r
 }  // namespace bpftime_amd
 
 extern "C" {
+
+int bpftime_amd_last_seq_tier(void) { return bpftime_amd::g_last_seq_tier; }
 
 struct ebpf_vm *ebpf_create(const char *vm_name) {
   if (!vm_name || strcmp(vm_name, "mi355x") != 0) return nullptr;

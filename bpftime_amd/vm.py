@@ -633,6 +633,13 @@ def uprobe_dispatch_plan(flags: int = 0) -> int:
     return rc
 
 
+def last_seq_tier() -> int:
+    """The tier that ran the callbacks of this host thread's most recent
+    thread-ordered dispatch, syscall or uprobe (bpftime_amd_last_seq_tier): 1
+    the asm tier, 0 the C++ tier, -1 before any.  Diagnostic."""
+    return lib().bpftime_amd_last_seq_tier()
+
+
 def syscall_attach(prog_fd: int, sys_nr: int, enter: bool = True) -> int:
     """A program on the sys_enter / sys_exit tracepoint of sys_nr (-1: every
     syscall; syscall_trace_attach_impl.cpp:121-166): the attach id."""

@@ -704,6 +704,15 @@ int64_t bpftime_amd_uprobe_dispatch_events(const struct bpftime_amd_call_records
  * would give (both plan flags, a pair that may not commute, a thread-ordered
  * refusal). */
 int bpftime_amd_uprobe_dispatch_plan(uint32_t flags);
+/* The tier that ran the callbacks of the calling host thread's most recent
+ * thread-ordered dispatch (BPFTIME_AMD_DISPATCH_THREADS), of syscall records,
+ * of recorded calls or of an event list: 1 the asm tier (LDS
+ * stacks, the hand-written threaded code), 0 the C++ tier, -1 when this thread
+ * has queued none.  Thread-local; set when the launch is queued.  Both tiers
+ * compute the same: this is a diagnostic for tests and measurements
+ * (BPFTIME_AMD_SEQ_ASM=1 / 0 forces a tier; a program with a stack of more than
+ * 64 B keeps the whole dispatch in the C++ tier either way). */
+int bpftime_amd_last_seq_tier(void);
 /* The last EBPF_BATCH_TIMED dispatch, summed over its attachments: the time of
  * the count + scan launches, of the gather launches (ms, stream events), and
  * the rows gathered.  After a thread-ordered dispatch: the thread grouping's

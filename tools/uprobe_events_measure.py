@@ -10,9 +10,13 @@ warm-ups each:
   3. the same on a nested trace of the same event count: per thread the calls
      form chains one to four deep (E E E R R R), so the function recurses.
 Prints one JSON line per dispatch; with a path argument also writes the
-measurement file."""
+measurement file.  --tiers asm,cpp takes every dispatch once per execution tier
+(BPFTIME_AMD_SEQ_ASM, read per dispatch), all of them alternately, and prints a
+line per dispatch and tier; the default is the tier the library chooses."""
+import argparse
 import ctypes as C
 import json
+import os
 import statistics
 import sys
 
@@ -57,7 +61,15 @@ def up(a):
     return dev.DeviceBuffer.from_array(np.ascontiguousarray(a).view(np.uint8).reshape(-1))
 
 
+TIER_ENV = {"auto": None, "asm": "1", "cpp": "0"}
+
+
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("path", nargs="?")
+    ap.add_argument("--tiers", default="auto")
+    args = ap.parse_args()
+    tiers = args.tiers.split(",")
     rng = np.random.default_rng(11)
     owner = rng.integers(0, THREADS, N)
     host = {"func": np.full(N, FUNC, dtype=np.uint64),
@@ -85,34 +97,43 @@ def main():
               2 * N)]
     L = dev.lib()
     gm, km, rows = C.c_float(), C.c_float(), C.c_uint64()
-    group, kern = {c[0]: [] for c in cases}, {c[0]: [] for c in cases}
+    keys = [(c[0], t) for c in cases for t in tiers]
+    group, kern, ran = {k: [] for k in keys}, {k: [] for k in keys}, {k: set() for k in keys}
     for it in range(WARM + REPS):
-        for name, run, want_rows in cases:               # alternately: a drift hits the three alike
-            assert run() == 0
-            L.bpftime_amd_uprobe_last_ms(C.byref(gm), C.byref(km), C.byref(rows))
-            assert rows.value == want_rows
-            if it >= WARM:
-                group[name].append(gm.value)
-                kern[name].append(km.value)
+        for name, run, want_rows in cases:               # alternately: a drift hits them all alike
+            for t in tiers:
+                if TIER_ENV[t] is None:
+                    os.environ.pop("BPFTIME_AMD_SEQ_ASM", None)
+                else:
+                    os.environ["BPFTIME_AMD_SEQ_ASM"] = TIER_ENV[t]
+                assert run() == 0
+                ran[name, t].add(dev.last_seq_tier())
+                L.bpftime_amd_uprobe_last_ms(C.byref(gm), C.byref(km), C.byref(rows))
+                assert rows.value == want_rows
+                if it >= WARM:
+                    group[name, t].append(gm.value)
+                    kern[name, t].append(km.value)
     total = int(np.frombuffer(mh.lookup(b"\0\0\0\0"), dtype=np.uint32).sum())
-    assert total == 3 * (WARM + REPS) * N, total          # every call of every dispatch was filed
+    assert total == 3 * len(tiers) * (WARM + REPS) * N, total   # every call of every dispatch was filed
     lines = []
-    for name, _, _ in cases:
-        g, k = statistics.median(group[name]), statistics.median(kern[name])
+    for name, t in keys:
+        g, k = statistics.median(group[name, t]), statistics.median(kern[name, t])
         lines.append(json.dumps({
-            "case": name, "records": N, "events": 2 * N, "threads": THREADS, "callbacks": 2 * N,
+            "case": name, "tier": t, "tier_ran": sorted(ran[name, t]), "records": N, "events": 2 * N,
+            "threads": THREADS, "callbacks": 2 * N,
             "nesting_depth": depth if name == "events_nested" else 1,
-            "kernel_ms_median": round(k, 4), "kernel_ms_min": round(min(kern[name]), 4),
-            "kernel_ms_max": round(max(kern[name]), 4), "grouping_ms_median": round(g, 4),
-            "grouping_ms_min": round(min(group[name]), 4), "grouping_ms_max": round(max(group[name]), 4),
+            "kernel_ms_median": round(k, 4), "kernel_ms_min": round(min(kern[name, t]), 4),
+            "kernel_ms_max": round(max(kern[name, t]), 4), "grouping_ms_median": round(g, 4),
+            "grouping_ms_min": round(min(group[name, t]), 4), "grouping_ms_max": round(max(group[name, t]), 4),
             "dispatch_Mcallbacks_per_s": round(2 * N / (g + k) / 1e3, 1)}))
     for line in lines:
         print(line, flush=True)
-    if len(sys.argv) > 1:
-        with open(sys.argv[1], "w") as f:
+    if args.path:
+        with open(args.path, "w") as f:
             f.write("# tools/uprobe_events_measure.py on one MI355X: the funclatency pair on one function, 2^20 "
                     "recorded calls evenly over 4096 recorded threads; stream events, median of 7 dispatches after 3 "
-                    "warm-ups, the three dispatches taken alternately in one process.\n"
+                    "warm-ups, the three dispatches (per asked tier; tier_ran: bpftime_amd_last_seq_tier) taken alternately "
+                    "in one process.\n"
                     "# calls: bpftime_amd_uprobe_dispatch | BPFTIME_AMD_DISPATCH_THREADS (the baseline); events_flat: "
                     "bpftime_amd_uprobe_dispatch_events on E(0,0), E(0,1), E(1,0), ... over the same records; "
                     "events_nested: the same event count, per thread chains of 1..4 nested calls of the function.\n"
