@@ -56,6 +56,22 @@ class CallRecords(C.Structure):  # include/bpftime_amd.h struct bpftime_amd_call
                 ("stack_fixed_depth", C.c_uint32), ("stack_max_depth", C.c_uint32), ("count", C.c_uint64)]
 
 
+class XdpDesc(C.Structure):  # include/ebpf-vm.h struct ebpf_xdp_desc
+    _fields_ = [("addr", C.c_uint64), ("len", C.c_uint32), ("options", C.c_uint32)]
+
+
+class XdpCompleteArgs(C.Structure):  # include/bpftime_amd.h struct bpftime_amd_xdp_complete_args
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("count", C.c_uint64),
+                ("verdicts", C.c_void_p), ("descs", C.c_void_p), ("data_off_out", C.c_void_p),
+                ("len_out", C.c_void_p), ("umem", C.c_void_p), ("stride", C.c_uint64),
+                ("umem_bytes", C.c_uint64), ("stream", C.c_void_p),
+                ("out", C.c_void_p * 5), ("index_out", C.c_void_p * 5), ("cap", C.c_uint64 * 5),
+                ("frame_mask", C.c_uint32), ("gather_mask", C.c_uint32), ("counts", C.c_void_p),
+                ("host_counts", u32p), ("gather", C.c_void_p), ("gather_stride", C.c_uint64),
+                ("gather_cap", C.c_uint64), ("gather_descs", C.c_void_p), ("gather_index", C.c_void_p),
+                ("gather_count", C.c_void_p), ("gather_skipped", C.c_void_p), ("host_gather", u32p)]
+
+
 class PerfEvent(C.Structure):
     """struct bpftime_amd_perf_event (include/bpftime_amd.h)"""
     _fields_ = [("type", C.c_int), ("pid", C.c_int), ("enabled", C.c_int), ("tracepoint_id", C.c_int32),
@@ -174,6 +190,10 @@ SIGNATURES = [
     ("bpftime_amd_uprobe_dispatch_plan", C.c_int, [C.c_uint32]),
     ("bpftime_amd_last_seq_tier", C.c_int, []),
     ("bpftime_amd_uprobe_last_ms", C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), u64p]),
+    ("bpftime_amd_xdp_complete", C.c_int, [C.POINTER(XdpCompleteArgs)]),
+    ("bpftime_amd_xdp_complete_from_batch", C.c_int, [C.POINTER(EbpfBatch), C.POINTER(XdpCompleteArgs)]),
+    ("bpftime_amd_xdp_complete_tile", C.c_uint32, []),
+    ("bpftime_amd_xdp_complete_scan_tiles", C.c_uint32, []),
     ("bpftime_amd_enable_trace_printk", C.c_int, [C.c_int]),
     ("bpftime_amd_trace_read", C.c_int64, [C.POINTER(TraceLine), C.c_uint64, C.c_void_p, C.c_uint64, u64p]),
     ("bpftime_amd_syscall_attach", C.c_int, [C.c_int, C.c_int64]),

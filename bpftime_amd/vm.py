@@ -14,7 +14,8 @@ from typing import Optional
 import numpy as np
 
 from . import isa
-from ._lib import BpfLinkCreateArgs, BpfMapAttr, CallRecords, EbpfBatch, LaunchInfo, SysRecords, TraceLine, lib
+from ._lib import (BpfLinkCreateArgs, BpfMapAttr, CallRecords, EbpfBatch, LaunchInfo, SysRecords, TraceLine,
+                   XdpCompleteArgs, lib)
 from ._lib import PerfEvent as PerfEventRec
 
 CTX_RAW, CTX_XDP, CTX_SYSCALL, CTX_SYSCALL_EXIT, CTX_UPROBE = 0, 1, 2, 3, 4
@@ -506,6 +507,64 @@ class VM:
             self.close()
         except Exception:
             pass
+
+
+XDP_ABORTED, XDP_DROP, XDP_PASS, XDP_TX, XDP_REDIRECT = 0, 1, 2, 3, 4
+XDP_COMPLETE_SYNC = 0x1
+XDP_FRAME_MASK_DEFAULT = (1 << XDP_PASS) | (1 << XDP_TX) | (1 << XDP_REDIRECT)
+
+
+def xdp_complete_tile() -> int:
+    """Units per workgroup tile of the completion kernels."""
+    return lib().bpftime_amd_xdp_complete_tile()
+
+
+def xdp_complete_scan_tiles() -> int:
+    """Tiles per pass of the completion's tile-offset scan."""
+    return lib().bpftime_amd_xdp_complete_scan_tiles()
+
+
+def xdp_complete(count: int, verdicts: Optional[DeviceBuffer], stride: int, umem_bytes: int,
+                 descs: Optional[DeviceBuffer] = None, data_off_out: Optional[DeviceBuffer] = None,
+                 len_out: Optional[DeviceBuffer] = None, umem: Optional[DeviceBuffer] = None, out=None,
+                 index_out=None, cap=None, frame_mask: int = XDP_FRAME_MASK_DEFAULT,
+                 counts: Optional[DeviceBuffer] = None, gather=None, gather_stride: int = 0, gather_cap: int = 0,
+                 gather_mask: int = 0, gather_descs: Optional[DeviceBuffer] = None,
+                 gather_index: Optional[DeviceBuffer] = None, gather_count: Optional[DeviceBuffer] = None,
+                 gather_skipped: Optional[DeviceBuffer] = None, stream: int = 0, sync: bool = True):
+    """bpftime_amd_xdp_complete after an EBPF_CTX_XDP batch on the same
+    stream: per verdict class (XDP_ABORTED .. XDP_REDIRECT) a descriptor list
+    in unit order.  out / index_out: five DeviceBuffers or None each ({u64
+    addr, u32 len, u32 options} entries / u32 unit indices), cap: five entry
+    counts.  The classes in frame_mask get their frames as the program left
+    them, the others the chunk to hand back to the FILL ring.  gather: a
+    DeviceBuffer or a pinned-host address that receives the frames of the
+    classes in gather_mask, packed gather_stride apart in unit order.
+    Returns, when sync, the five totals (not clamped to cap) -- with a gather,
+    (totals, gathered, skipped); without sync None (read `counts`)."""
+    p = lambda b: (b.ptr if hasattr(b, "ptr") else int(b)) if b else None  # noqa: E731
+    a = XdpCompleteArgs(struct_size=C.sizeof(XdpCompleteArgs), flags=XDP_COMPLETE_SYNC if sync else 0, count=count,
+                        verdicts=p(verdicts), descs=p(descs), data_off_out=p(data_off_out), len_out=p(len_out),
+                        umem=p(umem), stride=stride, umem_bytes=umem_bytes, stream=stream or None,
+                        frame_mask=frame_mask, gather_mask=gather_mask, counts=p(counts), gather=p(gather),
+                        gather_stride=gather_stride, gather_cap=gather_cap, gather_descs=p(gather_descs),
+                        gather_index=p(gather_index), gather_count=p(gather_count),
+                        gather_skipped=p(gather_skipped))
+    for c in range(5):
+        a.out[c] = p(out[c]) if out else None
+        a.index_out[c] = p(index_out[c]) if index_out else None
+        a.cap[c] = cap[c] if cap else 0
+    host = (C.c_uint32 * 5)()
+    host_g = (C.c_uint32 * 2)()
+    if sync:
+        a.host_counts = C.cast(host, C.POINTER(C.c_uint32))
+        a.host_gather = C.cast(host_g, C.POINTER(C.c_uint32))
+    if lib().bpftime_amd_xdp_complete(C.byref(a)) < 0:
+        raise EbpfError(_err())
+    if not sync:
+        return None
+    totals = [int(x) for x in host]
+    return (totals, int(host_g[0]), int(host_g[1])) if gather else totals
 
 
 def enable_trace_printk(on: bool = True) -> bool:

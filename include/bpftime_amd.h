@@ -719,6 +719,105 @@ int bpftime_amd_last_seq_tier(void);
  * time, the replay launch's, and the records.  Any out pointer may be NULL. */
 int bpftime_amd_uprobe_last_ms(float *count_ms, float *gather_ms, uint64_t *rows);
 
+/* ---- XDP completion (XDP completion; csrc/xdp_complete.cpp) ----
+ * What a runner does after an EBPF_CTX_XDP batch, on the device: the batch's
+ * per-unit outputs become one descriptor list per verdict, each in unit order
+ * (a flow's packets leave in the order they came), and optionally the frames
+ * of chosen lists are packed into one buffer for a single copy to the host.
+ * Queue it on the batch's stream, after the batch; no sync is needed between.
+ *
+ * Unit i's frame address is descs[i].addr, or i * stride when descs is NULL
+ * (strided mode).  After the program its frame is [addr + off, addr + off +
+ * len): off = data_off_out[i] (0 without the array), len = len_out[i]
+ * (descs[i].len without it); strided mode needs both arrays.  Its chunk is
+ * [base, base + stride), base = addr - addr % stride.
+ *
+ * Class of a unit: its verdict when that is <= 4 (XDP_ABORTED 0, DROP 1, PASS
+ * 2, TX 3, REDIRECT 4), 0 for every other value; and 0 whatever the verdict
+ * when the frame does not lie inside its chunk or the chunk does not lie
+ * inside [0, umem_bytes) (64-bit arithmetic that does not wrap; such a unit
+ * is `confined`, below).
+ *
+ * List c (class c): out[c][k] and index_out[c][k] describe the k-th unit of
+ * class c in ascending unit index, for k < cap[c]; nothing is written at or
+ * past cap[c]; either pointer may be NULL (both: the class is only counted).
+ * index_out holds the unit index.  The entry of a unit whose class is in
+ * frame_mask (bit c = class c) is its frame {addr + off, len, options}
+ * (options copied from descs[i], 0 in strided mode); of any other unit, and of
+ * every confined unit, the chunk to hand back to the FILL ring {base, 0, 0} --
+ * or {addr, 0, 0} when the chunk is outside the umem.  counts (device u32[5],
+ * may be NULL) receives the classes' totals, not clamped to cap.
+ *
+ * Gather (gather non-NULL; a device or pinned-host pointer): the units whose
+ * class is in gather_mask (a subset of frame_mask), that are not confined and
+ * whose len <= gather_stride, form one merged list in ascending unit index.
+ * Its k-th frame's len bytes are copied from umem + addr + off to gather + k *
+ * gather_stride, gather_descs[k] = {k * gather_stride, len, options} and
+ * gather_index[k] = the unit, for k < gather_cap (either array may be NULL).
+ * Bytes [len, gather_stride) of a slot and slots at or past the list's length
+ * or gather_cap are not written.  gather_count (device u32, may be NULL): the
+ * list's length, not clamped.  A unit left out for len > gather_stride is
+ * counted in gather_skipped (device u32, may be NULL); it stays in its class
+ * list.
+ *
+ * BPFTIME_AMD_XDP_COMPLETE_SYNC: the call waits for the stream and writes the
+ * five totals to host_counts (host u32[5]) and, when non-NULL, the gather
+ * list's length and the skipped count to host_gather (host u32[2]).
+ *
+ * Returns 0, or -1 with a named bpftime_amd_last_error(), before anything is
+ * launched, for: args NULL or a struct_size that is not sizeof(struct
+ * bpftime_amd_xdp_complete_args); count >= 2^32; verdicts NULL; stride 0; an
+ * array that is not aligned to its element (4 B, descriptors 8 B); strided
+ * mode without data_off_out and len_out, or with count * stride >= 2^63;
+ * frame_mask with bits past the five classes; gather_mask outside frame_mask;
+ * gather without gather_stride or without umem; gather_cap * gather_stride >=
+ * 2^63; SYNC without host_counts.  count 0 succeeds with zero counts. */
+#define BPFTIME_AMD_XDP_COMPLETE_SYNC 0x1
+#define BPFTIME_AMD_XDP_CLASSES 5
+#define BPFTIME_AMD_XDP_FRAME_MASK_DEFAULT 0x1c /* PASS | TX | REDIRECT */
+struct bpftime_amd_xdp_complete_args {
+  uint32_t struct_size;       /* sizeof(struct bpftime_amd_xdp_complete_args) */
+  uint32_t flags;             /* BPFTIME_AMD_XDP_COMPLETE_* */
+  /* the finished batch (bpftime_amd_xdp_complete_from_batch fills these) */
+  uint64_t count;
+  const uint32_t *verdicts;
+  const struct ebpf_xdp_desc *descs;
+  const int32_t *data_off_out;
+  const uint32_t *len_out;
+  const void *umem;           /* device base of the frames (the batch's data); read by the gather only */
+  uint64_t stride;            /* the umem chunk size, or the slot stride */
+  uint64_t umem_bytes;
+  void *stream;
+  /* the lists */
+  struct ebpf_xdp_desc *out[BPFTIME_AMD_XDP_CLASSES];
+  uint32_t *index_out[BPFTIME_AMD_XDP_CLASSES];
+  uint64_t cap[BPFTIME_AMD_XDP_CLASSES];
+  uint32_t frame_mask;
+  uint32_t gather_mask;
+  uint32_t *counts;
+  uint32_t *host_counts;
+  /* the gather */
+  void *gather;
+  uint64_t gather_stride;
+  uint64_t gather_cap;
+  struct ebpf_xdp_desc *gather_descs;
+  uint32_t *gather_index;
+  uint32_t *gather_count;
+  uint32_t *gather_skipped;
+  uint32_t *host_gather;
+};
+int bpftime_amd_xdp_complete(const struct bpftime_amd_xdp_complete_args *args);
+/* Zeroes *args and fills struct_size, the batch half (count, verdicts, descs,
+ * data_off_out, len_out, umem, stride, umem_bytes -- count * stride in strided
+ * mode -- and stream) from an EBPF_CTX_XDP batch, and frame_mask with the
+ * default, so the two calls cannot disagree.  -1 (named) for a NULL pointer or
+ * a batch of another ctx kind. */
+int bpftime_amd_xdp_complete_from_batch(const struct ebpf_batch *batch, struct bpftime_amd_xdp_complete_args *args);
+/* Units per workgroup tile of the partition kernels, and tiles per pass of
+ * the tile-offset scan (for tests that pick sizes around them). */
+uint32_t bpftime_amd_xdp_complete_tile(void);
+uint32_t bpftime_amd_xdp_complete_scan_tiles(void);
+
 /* ---- attach plugins (attach/base_attach_impl/base_attach_impl.hpp:24-71,
  * attach/simple_attach_impl/simple_attach_impl.cpp:7-55; csrc/attach.cpp) ----
  * An attach entry is a program loaded on the device.  bpftime_amd_attach_run
