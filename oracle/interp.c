@@ -15,8 +15,9 @@
  * r10 = top of a 512-B stack (ebpf-vm.h:47-49), ALU32 results zero-extended,
  * shift counts masked to 31/63, div by zero -> 0, mod by zero -> dst
  * unchanged, helpers called as fn(r1..r5) leaving r1-r5 untouched, bounds
- * checking OFF (vm/example/main.c:32).  PARITY
- * UNPINNED for the arithmetic beyond the analytic KATs.
+ * checking OFF (vm/example/main.c:32).  The
+ * arithmetic beyond the analytic KATs is pinned to tests/_isa_model.py and
+ * the hand vectors of tests/test_isa_model.py.
  */
 #include "oracle.h"
 #include <errno.h>

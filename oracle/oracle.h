@@ -13,9 +13,10 @@
  *
  * Parity status: the interpreter arithmetic lives in iovisor/ubpf, an
  * un-vendored empty submodule (.gitmodules:16-18, pinned commit unknown), and
- * no executing reference test covers it -> the interpreter is "parity
- * unpinned" except for the analytic KATs (vm/example/bpf_progs.h,
- * .github/assets/sum.bpf.o semantics).  Map semantics are pinned by ports of
+ * no executing reference test covers it beyond the analytic KATs
+ * (vm/example/bpf_progs.h, .github/assets/sum.bpf.o semantics) -> the
+ * interpreter is pinned to a model written from the ISA's rules
+ * (tests/_isa_model.py, tests/test_isa_model.py).  Map semantics are pinned by ports of
  * runtime/unit-test/maps/ (test_*.cpp) assertions (tests/test_oracle_maps.py).
  */
 #ifndef BPFTIME_AMD_ORACLE_H
