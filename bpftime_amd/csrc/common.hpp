@@ -376,10 +376,21 @@ constexpr uint32_t kFrameRematShift = 50;
 // call + both masks' words, and the depths to keep the block's residency)
 constexpr uint32_t kTailLdsMax = 4;  // depths held in LDS at most
 
-// Map effects of a program (loader.hpp FastForm::map_fx): loads (and lookups), counter adds whose order no
-// one observes (fused ld/add/st and atomic adds without fetch), every other
-// write (stores, fetching or non-add atomics, update / delete / ring calls)
-constexpr uint8_t FX_READ = 1, FX_ADD = 2, FX_WRITE = 4;
+// Map effects of a program (loader.hpp FastForm::map_fx): lookups and other
+// helper reads (FX_READ), counter adds whose order no one observes (FX_ADD:
+// fused ld/add/st and atomic adds without fetch), writes whose order shows
+// (FX_WRITE: stores, fetching or non-add atomics, update / delete / ring
+// calls), loads of a map's values (FX_LOAD: what a counter add beside it in
+// the same program may feed), and bpf_map_update_elem calls whose flags are
+// the constant BPF_NOEXIST and whose value is proven constant too (FX_INIT:
+// loader.cpp const_before / const_stack_before; whichever call comes first
+// inserts that value, the later ones change nothing; also bpf_get_stackid,
+// whose slots and returns a parallel batch leaves as the serial run does,
+// DESIGN.md §6 "Stack traces").  Between two programs FX_INIT
+// counts as a write, and a counter add clashes with FX_LOAD only (a lookup
+// alone sees a key's presence, which no add changes); the other splits matter
+// to one program against itself (syscall_dispatch.cpp first_map_conflict).
+constexpr uint8_t FX_READ = 1, FX_ADD = 2, FX_WRITE = 4, FX_LOAD = 8, FX_INIT = 16;
 
 // Context kinds for a batch
 constexpr uint32_t CTX_RAW = 0;      // r1 = unit memory, r2 = length
@@ -534,8 +545,9 @@ struct SeqProg {
   const DInsn *prog;
   const FInsn *fast;    // its ORDERED link (every counter add reaches memory at once)
   int64_t sys_nr;       // -1: every syscall
-  uint32_t enter;       // 1 sys_enter, 0 sys_exit
-  uint32_t task;        // its VM's identity: SeqParams::tasks[task]
+  uint16_t enter;       // 1 sys_enter, 0 sys_exit
+  uint16_t task;        // its VM's identity: SeqParams::tasks[task]
+  uint32_t step_limit;  // its VM's: max executed insns per callback
 };
 // A VM's task identity (bpf_get_current_uid_gid / bpf_get_current_comm)
 struct SeqTask {
@@ -575,7 +587,6 @@ struct SeqParams {
   uint32_t ncpu;
   uint32_t checked;
   uint64_t arena_lo, arena_hi;
-  uint64_t step_limit;
   uint64_t lru_seq;
   uint64_t pid_tgid;      // 64-B records: the dispatching thread's
   uint32_t *err_count;    // failed callbacks
@@ -611,7 +622,7 @@ struct UpSeqProg {
   // not fit the kernel arguments beside the identities
   uint8_t kind;
   uint16_t task;        // its VM's identity: UpSeqParams::tasks[task]
-  uint32_t pad;
+  uint32_t step_limit;  // its VM's: max executed insns per callback
 };
 static_assert(sizeof(UpSeqProg) == 40, "UpSeqProg is read with scalar loads");
 // One wave per block: the wave stages its 64 current records together between
@@ -648,7 +659,6 @@ struct UpSeqParams {
   uint32_t ncpu;
   uint32_t checked;
   uint64_t arena_lo, arena_hi;
-  uint64_t step_limit;
   uint64_t lru_seq;
   uint64_t pid_tgid;      // records without callers: the dispatching thread's
   uint32_t *err_count;    // failed callbacks

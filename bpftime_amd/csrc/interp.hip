@@ -1504,7 +1504,7 @@ __global__ __launch_bounds__(kBlock) void k_sys_seq(SeqParams p) {
   c.dummy = (uint64_t)(uintptr_t)&Rf[11 * kBlock + tid];
   c.verdicts = nullptr;
   c.rets = nullptr;
-  c.step_limit = p.step_limit > 0xffffffffull ? 0xffffffffu : (uint32_t)p.step_limit;
+  c.step_limit = 0;  // (per callback: SeqProg / UpSeqProg step_limit)
   c.c0a = c.c0d = c.c1a = c.c1d = 0;
   c.c0s = c.c1s = 0;
   uint64_t k = 0, end = 0;
@@ -1594,6 +1594,7 @@ __global__ __launch_bounds__(kBlock) void k_sys_seq(SeqParams p) {
       c.pc = 0;
       c.lpc = 0;
       c.steps = 0;
+      c.step_limit = __builtin_amdgcn_readfirstlane(sp->step_limit);  // its own VM's
       c.unit = idx;
       int32_t miss_fd = -1;
       uint64_t miss_hash = 0;
@@ -1833,7 +1834,7 @@ __global__ __launch_bounds__(kUpSeqBlock) void k_up_seq(UpSeqParams p) {
   c.dummy = (uint64_t)(uintptr_t)&Rf[11 * kBlock + tid];
   c.verdicts = nullptr;
   c.rets = nullptr;
-  c.step_limit = p.step_limit > 0xffffffffull ? 0xffffffffu : (uint32_t)p.step_limit;
+  c.step_limit = 0;  // (per callback: SeqProg / UpSeqProg step_limit)
   c.c0a = c.c0d = c.c1a = c.c1d = 0;
   c.c0s = c.c1s = 0;
   uint64_t k = 0, end = 0;
@@ -1934,6 +1935,7 @@ __global__ __launch_bounds__(kUpSeqBlock) void k_up_seq(UpSeqParams p) {
         c.pc = 0;
         c.lpc = 0;
         c.steps = 0;
+        c.step_limit = __builtin_amdgcn_readfirstlane(sp->step_limit);  // its own VM's
         c.unit = idx;
         int32_t miss_fd = -1;
         uint64_t miss_hash = 0;

@@ -1546,6 +1546,64 @@ uint32_t lcache_sets() {
   return sets;
 }
 
+// Whether register r holds a constant before instruction i, set by a `mov r,
+// imm` in i's own straight-line run (no call, jump or join in between): the
+// pointer kinds keep no scalars, and map_effects asks only for the flags of a
+// bpf_map_update_elem, which compilers set right before the call.
+static bool const_before(const std::vector<DInsn> &prog, const std::vector<bool> &joins, size_t i, int r, int64_t &v) {
+  if (joins[i]) return false;  // a jump straight to i brings its own r
+  for (size_t j = i; j-- > 0;) {
+    const DInsn &d = prog[j];
+    if (d.op == X_CALL || d.op == X_EXIT || d.op == X_JA || is_cond_jump(d.op)) return false;
+    RegSet u, df;
+    use_def(d, u, df);
+    if (df & (1u << r)) {
+      if (d.op != X_MOV || (d.aux & A_SRCREG) || d.dst != r) return false;
+      v = (d.aux & A_W32) ? (int64_t)(uint32_t)d.imm : (int64_t)d.imm;
+      return true;
+    }
+    if (joins[j]) return false;  // another path enters here with its own r
+  }
+  return false;
+}
+
+// Whether the `len` stack bytes at fp + at hold constants before instruction
+// i: every byte written by a store of an immediate (`st`) in i's own
+// straight-line run, with no other store that may reach them after it.  What
+// a bpf_map_update_elem with BPF_NOEXIST inserts must be the same for every
+// call of the program before the insert counts as order-free (FX_INIT): the
+// zeroed value of bpf_map_lookup_or_try_init is, a first-seen timestamp is not.
+static bool const_stack_before(const std::vector<DInsn> &prog, const std::vector<std::vector<PVal>> &in,
+                               const std::vector<bool> &joins, size_t i, int64_t at, int64_t len) {
+  if (len <= 0 || len > 512 || joins[i]) return false;
+  std::vector<bool> done((size_t)len, false);  // bytes whose last store is already seen, a constant
+  int64_t left = len;
+  for (size_t j = i; j-- > 0 && left > 0;) {
+    const DInsn &d = prog[j];
+    if (d.op == X_CALL || d.op == X_EXIT || d.op == X_JA || is_cond_jump(d.op)) return false;
+    if (in[j][10].kind == P_UNDEF) continue;  // never runs (the tail of a fused ld/add/st)
+    if (d.op == X_ST || d.op == X_STX || d.op == X_ATOMIC || d.op == X_RMW_ADD) {
+      const PVal &b = in[j][d.dst];
+      const int64_t sz = 1 << ((d.aux >> A_SIZE_SHIFT) & 3);
+      if (b.kind != P_STK) {
+        // the unit's other memory and map values are not the stack; a base
+        // the kinds cannot place may be
+        if (b.kind != P_CTX && b.kind != P_PKT && b.kind != P_SLOT && b.kind != P_MAPVAL && b.kind != P_CONST)
+          return false;
+      } else {
+        for (int64_t o = (int64_t)b.k + d.off; o < (int64_t)b.k + d.off + sz; o++) {
+          if (o < at || o >= at + len || done[(size_t)(o - at)]) continue;
+          if (d.op != X_ST) return false;  // a register's value
+          done[(size_t)(o - at)] = true;
+          left--;
+        }
+      }
+    }
+    if (left > 0 && joins[j]) return false;  // another path enters here with its own stack
+  }
+  return left == 0;
+}
+
 // FastForm::map_fx from the pointer kinds: which maps each load, store,
 // atomic and map helper call reaches.  Accesses of the unit's own memory (its
 // stack, its ctx copy, packet / slot bytes) are not map effects; an access
@@ -1558,6 +1616,10 @@ static void map_effects(const std::vector<DInsn> &prog, const std::vector<std::v
     if (fd >= 0) out.map_fx[fd] |= bits;
     else out.any_fx |= bits;
   };
+  const uint8_t kLoad = FX_READ | FX_LOAD;  // a read of a map's values
+  std::vector<bool> joins(prog.size(), false);  // jump targets (const_before)
+  for (const DInsn &d : prog)
+    if ((d.op == X_JA || is_cond_jump(d.op)) && d.tgt < prog.size()) joins[d.tgt] = true;
   // the map a memory access through base kind b (+ off) reaches: fd, -1 any
   // map, -2 the unit's own memory
   auto target = [&](size_t i, const PVal &b, int64_t off, uint32_t sz) -> int32_t {
@@ -1584,7 +1646,7 @@ static void map_effects(const std::vector<DInsn> &prog, const std::vector<std::v
     switch (d.op) {
       case X_LDX: {
         const int32_t t = target(i, st[d.src], d.off, sz);
-        if (t != -2) mark(t, FX_READ);
+        if (t != -2) mark(t, kLoad);
         break;
       }
       case X_ST: case X_STX: {
@@ -1603,8 +1665,27 @@ static void map_effects(const std::vector<DInsn> &prog, const std::vector<std::v
         const PVal &m = st[1];
         const int32_t fd = m.kind == P_MAPFD ? m.id : -1;
         switch (d.hi) {
-          case 1: case 89: mark(fd, FX_READ); break;                    // map_lookup_elem, map_peek_elem
-          case 2: case 3: case 130: case 131: case 87: case 88: mark(fd, FX_WRITE); break;  // update, delete, ringbuf output / reserve, push, pop
+          case 1: mark(fd, FX_READ); break;                             // map_lookup_elem: no value is read yet
+          case 89: mark(fd, kLoad); break;                              // map_peek_elem
+          case 2: {
+            // map_update_elem: with the constant flags BPF_NOEXIST and a
+            // constant value on the stack an insert that never replaces and
+            // is the same whichever call makes it (FX_INIT), else a write
+            int64_t fl = 0;
+            const MapRec *mr = map_rec(fd);
+            const bool init = mr && const_before(prog, joins, i, 4, fl) && fl == 1 /*BPF_NOEXIST*/ &&
+                              st[3].kind == P_STK && const_stack_before(prog, in, joins, i, st[3].k, mr->value_size);
+            mark(fd, init ? FX_INIT : FX_WRITE);
+            break;
+          }
+          case 3: case 130: case 131: case 87: case 88: mark(fd, FX_WRITE); break;  // delete, ringbuf output / reserve, push, pop
+          case kRetHelper: break;  // a linked target's exit
+          case 12:
+            // bpf_tail_call: nothing of its own.  What the targets do is in
+            // the linked image (vm_api.cpp link_tail_image_locked), which this
+            // pass sees whole; the dispatches ask for the effects of that
+            // image (vm_map_effects) and send tail calls to no other plan
+            break;
           case 5: case 7: case 8: case 14: case 28: case 44: case 58: case 65: case 132: case 133: case 187: case 189:
           case 15: case 125: case 160: case 173: case 174:
             break;  // no map effects (132 / 133 finish a reservation 131 marked)
@@ -1616,7 +1697,7 @@ static void map_effects(const std::vector<DInsn> &prog, const std::vector<std::v
           case 36: {  // probe_write_user(dst, src, len): writes through r1, reads through r2
             const int32_t t1 = target(i, st[1], 0, 1), t2 = target(i, st[2], 0, 1);
             if (t1 != -2) mark(t1, FX_WRITE);
-            if (t2 != -2) mark(t2, FX_READ);
+            if (t2 != -2) mark(t2, kLoad);
             break;
           }
           case 25: {
@@ -1626,14 +1707,23 @@ static void map_effects(const std::vector<DInsn> &prog, const std::vector<std::v
             // every map when the kinds cannot place r2; reads through r4
             mark(st[2].kind == P_MAPFD ? st[2].id : -1, FX_WRITE);
             const int32_t t4 = target(i, st[4], 0, 1);
-            if (t4 != -2) mark(t4, FX_READ);
+            if (t4 != -2) mark(t4, kLoad);
             break;
           }
           case 27:
             // get_stackid(ctx, map, flags): the map handle is r2 -- a write of
             // the STACK_TRACE map it names (which stack a slot keeps is an
-            // effect of the order), of every map when the kinds cannot place r2
-            mark(st[2].kind == P_MAPFD ? st[2].id : -1, FX_WRITE);
+            // effect of the order), of every map when the kinds cannot place r2.
+            // Against the program's own other records the order is kept: a
+            // parallel batch leaves the slots and every call's return as
+            // the serial run does (the claim keys of helper_stackid and
+            // stack_commit.hip; launches with BPF_F_REUSE_STACKID or a
+            // program-side lookup / delete are refused outside ORDERED,
+            // vm_api.cpp st_launch_check; tests/test_gpu_stacktrace.py
+            // test_parallel_matches_the_serial_model holds ids, -EEXIST
+            // returns and slots against the serial model), so like a NOEXIST
+            // insert it is no write the program conflicts with itself on
+            mark(st[2].kind == P_MAPFD ? st[2].id : -1, st[2].kind == P_MAPFD ? FX_INIT : FX_WRITE);
             break;
           case 67: {  // get_stack(ctx, buf, size, flags): writes through r2
             const int32_t t2 = target(i, st[2], 0, 1);
@@ -1643,7 +1733,7 @@ static void map_effects(const std::vector<DInsn> &prog, const std::vector<std::v
           case 6: {  // trace_printk reads the format and what its %s arguments point to
             for (int r : {1, 3, 4, 5}) {
               const int32_t t = target(i, st[r], 0, 1);
-              if (t != -2) mark(t, FX_READ);
+              if (t != -2) mark(t, kLoad);
             }
             break;
           }
@@ -1652,11 +1742,11 @@ static void map_effects(const std::vector<DInsn> &prog, const std::vector<std::v
             // r3, strncmp reads through both: map effects when the pointer
             // is a map value's (or cannot be placed: any map)
             const int32_t t1 = target(i, st[1], 0, 1), t3 = target(i, st[3], 0, 1);
-            if (t1 != -2) mark(t1, d.hi == 182 ? FX_READ : FX_WRITE);
-            if (t3 != -2) mark(t3, FX_READ);
+            if (t1 != -2) mark(t1, d.hi == 182 ? kLoad : FX_WRITE);
+            if (t3 != -2) mark(t3, kLoad);
             break;
           }
-          default: mark(-1, FX_READ | FX_WRITE); break;                 // bpf_tail_call, anything else
+          default: mark(-1, kLoad | FX_WRITE); break;                   // anything else
         }
         break;
       }

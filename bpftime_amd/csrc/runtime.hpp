@@ -200,15 +200,29 @@ int syscall_attach_set_cookie(int id, uint64_t cookie);
 void uprobe_detach_all();
 // A loaded program's map effects (loader.hpp FastForm::map_fx, the syscall /
 // raw entry form): per map fd FX_* bits and the bits that may reach any map.
-// -1: no program loaded.
+// A program that calls bpf_tail_call answers for its linked image: itself and
+// every target its prog arrays name at the time of the call (a launch relinks
+// when a prog array changed since: a plan made from these effects holds only
+// while no host thread updates the prog arrays before the dispatch's last
+// launch, DESIGN.md §5 "Tail calls").  -1: no program loaded, or the image
+// did not link.
 int vm_map_effects(const ::ebpf_vm *vm, std::map<int32_t, uint8_t> &fx, uint8_t &any);
-// The commute analysis of the dispatches (syscall_dispatch.cpp): whether two
-// of the loaded programs may not commute -- both reach one map and one writes
-// it (a store, a fetching / non-add atomic, update / delete / ring calls) or
-// adds to it while the other reads it; counter adds commute with counter adds,
-// reads with reads; effects the loader cannot place reach every map.  1 with
-// the first such pair and the map's fd (-1: unplaced effects) in the non-null
-// outs, 0 none, -1 a program is not loaded.
+// Whether the loaded program calls bpf_tail_call: only the program-major
+// plans run it (the thread-ordered kernels hold no tail-call frames).
+bool vm_has_tail(const ::ebpf_vm *vm);
+// The commute analysis of the dispatches (syscall_dispatch.cpp).  Two of the
+// loaded programs may not commute when both reach one map and one writes it
+// (a store, a fetching / non-add atomic, update / delete / ring calls) or adds
+// to it while the other loads from its values; counter adds commute with
+// counter adds (and with lookups: an add changes no key's presence), reads
+// with reads.  One program may not commute with ITSELF -- the
+// program-major plans run all of one thread's records in parallel lanes --
+// when it writes a map other than by a bpf_map_update_elem whose flags are
+// the constant BPF_NOEXIST and whose value is constant, or both adds to a map and loads from its values;
+// lookup + NOEXIST init + counter add stays order-free.  Effects the loader
+// cannot place reach every map.  1 with the first such pair (first == second:
+// the program against itself) and the map's fd (-1: unplaced effects) in the
+// non-null outs, 0 none, -1 a program is not loaded.
 int first_map_conflict(const std::vector<const ::ebpf_vm *> &vms, size_t *first, size_t *second, int *map);
 // Whether a loaded program may reach a QUEUE / STACK map (loader.cpp
 // qs_call_sites): such a program does not commute with itself across

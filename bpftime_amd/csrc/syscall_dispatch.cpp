@@ -34,7 +34,15 @@
 // (the loader's map effects, loader.hpp FastForm::map_fx): one writes a map
 // the other reads or writes, or adds to a map the other reads.  syscount's
 // latency pair is the case (example/tracing/syscount/syscount.bpf.c:33-47,
-// 71-76: sys_enter stores start[tid], sys_exit reads it).
+// 71-76: sys_enter stores start[tid], sys_exit reads it).  One attachment
+// alone may not commute with itself either: program-major runs all of a
+// thread's records in parallel lanes, so a program that overwrites per-thread
+// state (start[tid] = ts), or reads back the counter it adds to, leaves
+// whatever the race left where the reference leaves the thread's last call's
+// value (first_map_conflict, below).  Programs that call bpf_tail_call run in
+// the program-major plan only: their effects are those of their linked image
+// (the targets known at dispatch time), and a set that would need the
+// thread-ordered plan is refused by name before anything is launched.
 // Host-side bookkeeping only; the work is on the device.
 #include <errno.h>
 #include <stdlib.h>
@@ -134,11 +142,8 @@ std::vector<Attach> ordered_attachments() {
   return order;
 }
 
-// Whether the attachments may not commute: two of them reach one map, and one
-// writes it (a store, a fetching / non-add atomic, update / delete / ring
-// calls) or adds to it while the other reads it.  Counter adds commute with
-// counter adds; reads with reads.  Programs whose accesses the loader cannot
-// place reach every map.  -1 when a program is not loaded.
+// Whether the attachments may not commute (runtime.hpp first_map_conflict):
+// two of them, or one with itself.  -1 when a program is not loaded.
 int conflicts(const std::vector<Attach> &order) {
   std::vector<const struct ebpf_vm *> vms;
   for (const Attach &a : order) vms.push_back(a.vm.get());
@@ -147,7 +152,21 @@ int conflicts(const std::vector<Attach> &order) {
 
 // 1 thread-ordered, 0 program-major, -1 error
 int plan_for(const std::vector<Attach> &order, uint32_t flags) {
-  if (flags & EBPF_BATCH_ORDERED) return 1;  // one lane, record order: the serial run
+  // bpf_tail_call runs in ebpf_exec_batch only (k_sys_seq holds no frames)
+  bool tail = false;
+  for (const Attach &a : order) tail |= bpftime_amd::vm_has_tail(a.vm.get());
+  auto tail_refusal = [](const std::string &why) {
+    return fail("an attached program calls bpf_tail_call, which only the program-major plan runs, and " + why +
+                    " (detach one, or dispatch them apart)",
+                EINVAL);
+  };
+  if (flags & EBPF_BATCH_ORDERED) {
+    // one lane, record order: the serial run.  A lone tail-calling program
+    // is one ORDERED ebpf_exec_batch, which is the same run
+    if (!tail) return 1;
+    if (order.size() == 1) return 0;
+    return tail_refusal("an EBPF_BATCH_ORDERED dispatch interleaves several attachments in the thread-ordered plan");
+  }
   // a program that pushes to or pops from a QUEUE / STACK does not commute,
   // and lanes in thread order are not record order across threads
   for (const Attach &a : order)
@@ -155,9 +174,13 @@ int plan_for(const std::vector<Attach> &order, uint32_t flags) {
       return fail("an attached program touches a QUEUE / STACK map: the dispatch runs it only with EBPF_BATCH_ORDERED",
                   EINVAL);
   if (flags & BPFTIME_AMD_DISPATCH_PROGRAMS) return 0;
-  if (flags & BPFTIME_AMD_DISPATCH_THREADS) return 1;
+  if (flags & BPFTIME_AMD_DISPATCH_THREADS)
+    return tail ? tail_refusal("BPFTIME_AMD_DISPATCH_THREADS asks for the thread-ordered plan") : 1;
   const int c = conflicts(order);
   if (c < 0) return fail("an attached program is not loaded", EINVAL);
+  if (c && tail)
+    return tail_refusal("the attachments may not commute (one writes a map another, or its own next call, reads or "
+                        "writes), which needs the thread-ordered plan");
   return c;
 }
 
@@ -248,7 +271,9 @@ int64_t dispatch_programs(const std::vector<Attach> &order, const Records &r, in
       unit = copy + r.ctx_off[ph];
     }
     b.ctx_kind = a.enter ? EBPF_CTX_SYSCALL : EBPF_CTX_SYSCALL_EXIT;
-    b.flags = (flags & (EBPF_BATCH_SYNC | EBPF_BATCH_UNCHECKED)) | (a.sys_nr >= 0 ? EBPF_BATCH_SYS_NR : 0u);
+    // (ORDERED reaches here with one tail-calling attachment only: plan_for)
+    b.flags = (flags & (EBPF_BATCH_SYNC | EBPF_BATCH_UNCHECKED | EBPF_BATCH_ORDERED)) |
+              (a.sys_nr >= 0 ? EBPF_BATCH_SYS_NR : 0u);
     b.count = n;
     b.data = const_cast<uint8_t *>(unit);
     b.stride = ustride;
@@ -308,11 +333,34 @@ int bpftime_amd::first_map_conflict(const std::vector<const struct ebpf_vm *> &v
   std::vector<Fx> fx(vms.size());
   for (size_t i = 0; i < vms.size(); i++)
     if (vm_map_effects(vms[i], fx[i].m, fx[i].any) < 0) return -1;
-  auto clash = [](uint8_t a, uint8_t b) {
-    return ((a & FX_WRITE) && b) || ((b & FX_WRITE) && a) || ((a & FX_ADD) && (b & FX_READ)) ||
-           ((b & FX_ADD) && (a & FX_READ));
+  // (a counter add changes no key's presence, which is all a lookup alone
+  // observes: it clashes with loads of the values, not with lookups)
+  const uint8_t W = FX_WRITE | FX_INIT;
+  auto clash = [=](uint8_t a, uint8_t b) {
+    return ((a & W) && b) || ((b & W) && a) || ((a & FX_ADD) && (b & FX_LOAD)) || ((b & FX_ADD) && (a & FX_LOAD));
   };
-  for (size_t i = 0; i < fx.size(); i++)
+  // One program against itself, record against record of one thread: a write
+  // whose result depends on the order (anything but FX_INIT, a NOEXIST insert
+  // of a value the loader proved constant: the first call inserts the same
+  // value whichever it is), or a counter add
+  // whose running value the program loads.  Lookups, NOEXIST inserts and
+  // counter adds together stay order-free (lookup-or-init, then count).
+  auto self_clash = [](uint8_t a) { return (a & FX_WRITE) || ((a & FX_ADD) && (a & FX_LOAD)); };
+  for (size_t i = 0; i < fx.size(); i++) {
+    {
+      int hit = -2;
+      if (self_clash(fx[i].any)) hit = -1;
+      for (const auto &kv : fx[i].m) {
+        if (hit != -2) break;
+        if (self_clash(kv.second | fx[i].any)) hit = kv.first;
+      }
+      if (hit != -2) {
+        if (first) *first = i;
+        if (second) *second = i;
+        if (map) *map = hit;
+        return 1;
+      }
+    }
     for (size_t j = i + 1; j < fx.size(); j++) {
       int hit = -2;  // -1: effects the loader could not place on a map
       if (clash(fx[i].any, fx[j].any)) hit = -1;
@@ -331,6 +379,7 @@ int bpftime_amd::first_map_conflict(const std::vector<const struct ebpf_vm *> &v
       if (map) *map = hit;
       return 1;
     }
+  }
   return 0;
 }
 

@@ -149,7 +149,10 @@ int first_conflict(const std::vector<Attach> &order, std::string *what) {
     return "'" + order[k].name + "' (prog fd " + std::to_string(order[k].prog_fd) + ", attachment " +
            std::to_string(order[k].id) + ")";
   };
-  *what = "programs " + who(i) + " and " + who(j) + " may not commute on " +
+  // (i == j: one program against itself, its calls of one thread in
+  // parallel lanes -- runtime.hpp first_map_conflict)
+  *what = (i == j ? "program " + who(i) + " may not commute with itself on "
+                  : "programs " + who(i) + " and " + who(j) + " may not commute on ") +
           (map < 0 ? std::string("a map the loader cannot place") : "map fd " + std::to_string(map)) +
           ": program-major order would differ from the per-call order (detach one, or dispatch them apart); "
           "BPFTIME_AMD_DISPATCH_THREADS runs them in the per-call order";
@@ -189,12 +192,10 @@ int plan_for(const std::vector<Attach> &order, uint32_t flags) {
     const std::string why = threads_refusal(order, flags);
     return why.empty() ? 1 : (int)fail(why, EINVAL);
   }
-  if (order.size() > 1) {
-    std::string what;
-    const int c = first_conflict(order, &what);
-    if (c < 0) return (int)fail("an attached program is not loaded", EINVAL);
-    if (c) return (int)fail(what, EINVAL);
-  }
+  std::string what;
+  const int c = first_conflict(order, &what);
+  if (c < 0) return (int)fail("an attached program is not loaded", EINVAL);
+  if (c) return (int)fail(what, EINVAL);
   return 0;
 }
 

@@ -1548,12 +1548,22 @@ int vm_prog_flags(const ::ebpf_vm *vm) {
 
 int vm_map_effects(const ::ebpf_vm *vm, std::map<int32_t, uint8_t> &fx, uint8_t &any) {
   if (!vm || !vm->impl->loaded) return -1;
-  auto im = vm->impl->image();
+  std::shared_ptr<Image> im;
+  {
+    // a tail-calling program's effects are its linked image's: the targets
+    // its prog arrays name now, appended to it (link_tail_image_locked), so
+    // the loader's pass over the image is the union over them
+    std::lock_guard<std::mutex> g(vm->impl->img_mu);
+    if (vm->impl->has_tail && vm->impl->link_tail_image_locked() < 0) return -1;
+    im = vm->impl->img;
+  }
   if (!im) return -1;
   fx = im->fr.map_fx;
   any = im->fr.any_fx;
   return 0;
 }
+
+bool vm_has_tail(const ::ebpf_vm *vm) { return vm && vm->impl->loaded && vm->impl->has_tail; }
 
 bool vm_touches_qs(const ::ebpf_vm *vm) {
   if (!vm || !vm->impl->loaded) return false;
@@ -1586,7 +1596,6 @@ struct SeqLaunch {
   bool may_delete = false, names_lpm = false, qs_adds = false, qs_takes = false, touches_lpm = false;
   std::vector<int> lpm_w;
   uint32_t lpm_updates = 0;
-  uint64_t steps = 0;
   uint32_t ntasks = 0;
   std::unique_lock<std::mutex> lpm_lk;
   std::string err;  // why the last call returned false / -1
@@ -1606,7 +1615,7 @@ struct SeqLaunch {
     for (const ::ebpf_vm *v : vms) {
       auto im = v->impl->image();
       if (!im) continue;
-      const uint8_t w = FX_WRITE | FX_ADD;
+      const uint8_t w = FX_WRITE | FX_INIT | FX_ADD;
       any = any || (im->fr.any_fx & w);
       for (const auto &kv : im->fr.map_fx)
         if ((kv.second & w) && kv.first >= 0 && kv.first < (int32_t)kMaxFds &&
@@ -1617,11 +1626,12 @@ struct SeqLaunch {
   }
 
   // One attached program: its image and ORDERED link, and the index of its
-  // VM's identity in `tasks` (one table entry per distinct identity).  `rec`:
+  // VM's identity in `tasks` (one table entry per distinct identity), and its
+  // VM's step limit.  `rec`:
   // the asm tier's link, with the kernel's caller / clock offsets (pid 0: the
   // C++ tier's)
   bool add(Mi355xVm *vm, bool no_kldx, RecOffs rec, SeqTask *tasks, const DInsn *&prog, const FInsn *&link,
-           uint32_t &task) {
+           uint32_t &task, uint32_t &step_limit) {
     auto im = vm->image();
     if (!vm->loaded || !im) return fail("an attached program is not loaded");
     if (vm->has_tail) return fail("an attached program calls bpf_tail_call (program-major dispatch runs it)");
@@ -1664,7 +1674,9 @@ struct SeqLaunch {
       lpm_updates += w.first == 2;
       if (std::find(lpm_w.begin(), lpm_w.end(), w.second) == lpm_w.end()) lpm_w.push_back(w.second);
     }
-    steps = std::max(steps, vm->step_limit);
+    // (each callback runs under its own VM's limit, as in the program-major
+    // plan: the kernels count in 32 bits)
+    step_limit = (uint32_t)std::min<uint64_t>(vm->step_limit, 0xffffffffull);
     keep.push_back(std::move(im));
     return true;
   }
@@ -1765,7 +1777,10 @@ int64_t seq_dispatch(const std::vector<SeqAttach> &progs, const SysLayout &lay, 
   const bool no_kldx = L.array_writes(vms) && progs.size() > 1;
   for (const SeqAttach &a : progs) {
     SeqProg &q = p.progs[p.nprogs++];
-    if (!L.add(a.vm->impl, no_kldx, fast ? kSeqRecOffs : RecOffs{}, p.tasks, q.prog, q.fast, q.task)) return fail(L.err);
+    uint32_t task = 0;
+    if (!L.add(a.vm->impl, no_kldx, fast ? kSeqRecOffs : RecOffs{}, p.tasks, q.prog, q.fast, task, q.step_limit))
+      return fail(L.err);
+    q.task = (uint16_t)task;
     q.sys_nr = a.sys_nr;
     q.enter = a.enter ? 1 : 0;
     // its attach cookie (a link's; a syscall tracepoint has no func_ip)
@@ -1784,7 +1799,6 @@ int64_t seq_dispatch(const std::vector<SeqAttach> &progs, const SysLayout &lay, 
   p.checked = (flags & EBPF_BATCH_UNCHECKED) ? 0 : 1;
   p.arena_lo = (uint64_t)(uintptr_t)r.arena;
   p.arena_hi = p.arena_lo + r.arena_size;
-  p.step_limit = L.steps;
   p.pid_tgid = ((uint64_t)(uint32_t)getpid() << 32) | (uint32_t)syscall(SYS_gettid);
   p.err_count = err;
   p.trace_log = trace_log().d;
@@ -1842,7 +1856,7 @@ int64_t useq_dispatch(const std::vector<USeqAttach> &progs, const UpSeqParams &r
   for (const USeqAttach &a : progs) {
     UpSeqProg &q = p.progs[p.nprogs++];
     uint32_t task = 0;
-    if (!L.add(a.vm->impl, no_kldx, fast ? kUpSeqRecOffs : RecOffs{}, p.tasks, q.prog, q.fast, task))
+    if (!L.add(a.vm->impl, no_kldx, fast ? kUpSeqRecOffs : RecOffs{}, p.tasks, q.prog, q.fast, task, q.step_limit))
       return fail(L.err);
     q.task = (uint16_t)task;
     q.func = a.func;
@@ -1857,7 +1871,6 @@ int64_t useq_dispatch(const std::vector<USeqAttach> &progs, const UpSeqParams &r
   p.checked = (flags & EBPF_BATCH_UNCHECKED) ? 0 : 1;
   p.arena_lo = (uint64_t)(uintptr_t)r.arena;
   p.arena_hi = p.arena_lo + r.arena_size;
-  p.step_limit = L.steps;
   p.pid_tgid = ((uint64_t)(uint32_t)getpid() << 32) | (uint32_t)syscall(SYS_gettid);
   p.err_count = err;
   p.trace_log = trace_log().d;

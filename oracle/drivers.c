@@ -157,7 +157,15 @@ void orc_sys_reset(void)
 }
 
 /* run_callbacks (:41-53) over one callback set: each on its own ctx copy,
- * exec failures ignored */
+ * exec failures ignored (counted for orc_sys_failed: what the device's
+ * dispatch returns as its failed-callback count) */
+static uint64_t g_sys_failed;
+
+uint64_t orc_sys_failed(void)
+{
+	return g_sys_failed;
+}
+
 static void run_set(int enter, int global, int64_t nr, const void *ctx, size_t len)
 {
 	for (int i = 0; i < g_sys_n; i++) {
@@ -166,7 +174,8 @@ static void run_set(int enter, int global, int64_t nr, const void *ctx, size_t l
 		uint8_t copy[64];
 		memcpy(copy, ctx, len);
 		uint64_t v;
-		(void)orc_vm_exec(g_sys[i].vm, copy, len, &v);
+		if (orc_vm_exec(g_sys[i].vm, copy, len, &v) < 0)
+			g_sys_failed++;
 	}
 }
 
@@ -182,6 +191,7 @@ int orc_sys_dispatch(const uint8_t *recs, uint64_t n, uint32_t rec_size, int64_t
 {
 	if (rec_size != 64 && rec_size != 96 && rec_size != 128)
 		return -22;
+	g_sys_failed = 0;
 	for (uint64_t i = 0; i < n; i++) {
 		const uint8_t *r = recs + i * rec_size;
 		const struct trace_event_raw_sys_enter *er = (const void *)r;

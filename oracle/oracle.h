@@ -138,6 +138,8 @@ int orc_sys_attach(struct orc_vm *vm, int64_t sys_nr, int is_enter);
 int orc_sys_detach(int id);
 void orc_sys_reset(void);
 int orc_sys_dispatch(const uint8_t *recs, uint64_t n, uint32_t rec_size, int64_t *out);
+/* callbacks whose exec failed during the last orc_sys_dispatch */
+uint64_t orc_sys_failed(void);
 /* the thread's return callback (base_attach_impl.hpp:18-19), internal */
 struct orc_retval_cb {
 	int active, overridden;

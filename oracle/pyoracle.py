@@ -76,6 +76,7 @@ def lib():
             "orc_sys_detach": (C.c_int, [C.c_int]),
             "orc_sys_reset": (None, []),
             "orc_sys_dispatch": (C.c_int, [vp, u64, u32, vp]),
+            "orc_sys_failed": (u64, []),
         }
         for k, (r, a) in sig.items():
             f = getattr(l, k)
@@ -289,6 +290,12 @@ class OracleSyscallDispatch:
         if rc < 0:
             raise ValueError(f"orc_sys_dispatch: {rc}")
         return out
+
+    @staticmethod
+    def failed() -> int:
+        """Callbacks whose exec failed during the last dispatch (the device's
+        failed-callback count)."""
+        return lib().orc_sys_failed()
 
 
 def prog_create(fd: int, code: bytes) -> int:

@@ -249,7 +249,11 @@ def test_plan_selection(fresh_runtime):
     dev.syscall_detach(ids.pop())
     assert dev.syscall_dispatch_plan() == 0
     att(programs.syscount_enter(start.fd, ro.fd), -1, True)
-    assert dev.syscall_dispatch_plan() == 0            # syscount_exit without the latency path never reads start
+    # syscount_exit without the latency path never reads start, but
+    # syscount_enter alone overwrites start[tid] call after call: in parallel
+    # lanes the last call's clock would not be the one that stays
+    # (test_syscount_enter_without_latency_keeps_the_last_clock)
+    assert dev.syscall_dispatch_plan() == 1
     att(programs.syscount_exit(data.fd, ro.fd, start.fd), -1, False)
     assert dev.syscall_dispatch_plan() == 1            # ... with it, it does
     assert dev.syscall_dispatch_plan(dev.DISPATCH_PROGRAMS) == 0
@@ -258,6 +262,37 @@ def test_plan_selection(fresh_runtime):
         dev.syscall_detach(i)
     att(programs.syscount_exit(data.fd, ro.fd), -1, False)
     assert dev.syscall_dispatch_plan(dev.DISPATCH_THREADS) == 1
+
+
+@pytest.mark.parametrize("threads", [8, 200])
+def test_syscount_enter_without_latency_keeps_the_last_clock(fresh_oracle, fresh_runtime, threads):
+    """syscount_enter beside syscount_exit WITHOUT the latency path: no pair
+    conflict, yet start[tid] must end as the clock of the thread's last call
+    (the reference runs a thread's calls one after another): the automatic
+    plan is thread-ordered, and start, data and the returns are the oracle's."""
+    po, dev = fresh_oracle, fresh_runtime
+    (ostart, odata, oro), (dstart, ddata, dro) = make_maps(
+        [(HASH, 4, 8, 10240), (HASH, 4, 32, 10240), (ARRAY, 4, programs.SYSCOUNT_RODATA, 1)], po, dev)
+    ro = programs.syscount_rodata()
+    assert oro.update(b"\0" * 4, ro) == 0 and dro.update(b"\0" * 4, ro) == 0
+    o = po.OracleSyscallDispatch()
+    _attach(dev, o, programs.syscount_enter(dstart.fd, dro.fd), -1, True)
+    _attach(dev, o, programs.syscount_exit(ddata.fd, dro.fd), -1, False)
+    assert dev.syscall_dispatch_plan() == 1
+    n = 1 << 12
+    recs = gen.syscall_records_timed(n, threads=threads)
+    d = dev.DeviceBuffer.from_array(recs)
+    out = dev.DeviceBuffer(8 * n)
+    assert dev.syscall_dispatch(d, n, record_size=dev.SYSCALL_RECORD_TIMED, out=out) == 0
+    assert (out.download(np.int64) == o.dispatch(recs)).all()
+    assert dstart.hash_items() == ostart.items() and len(ostart.items()) == threads
+    assert ddata.hash_items() == odata.items()
+    # the last live call of each thread left its clock
+    w = recs.view(np.uint64).reshape(n, 16)
+    live = ~np.isin(w[:, 1], [60, 231])
+    for tid, v in ostart.items().items():
+        at = np.flatnonzero(live & ((w[:, 11] & np.uint64(0xFFFFFFFF)) == np.uint64(struct.unpack("<I", tid)[0])))
+        assert struct.unpack("<Q", v)[0] == int(w[at[-1], 12])
 
 
 def _ktime_sum(fd, slot):
