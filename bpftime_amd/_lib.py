@@ -279,6 +279,10 @@ SIGNATURES = [
 # symbols outside include/*.h that the Python layer also uses
 EXTRA = [
     ("bpftime_amd_vm_error", C.c_char_p, [C.c_void_p]),
+    # csrc/group.hip: the thread grouping of the thread-ordered dispatches (a hipError_t)
+    ("bpftime_amd_group_scratch_bytes", C.c_size_t, [C.c_uint64]),
+    ("bpftime_amd_group_threads", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p),
+                                            C.POINTER(C.c_void_p), u64p, C.c_void_p]),
 ]
 
 _lib = None

@@ -699,6 +699,28 @@ def last_seq_tier() -> int:
     return lib().bpftime_amd_last_seq_tier()
 
 
+def group_threads(keys: Optional[DeviceBuffer], n: int, stride: int = 8, offset: int = 0):
+    """bpftime_amd_group_threads (csrc/group.hip) on the null stream: the
+    grouping both thread-ordered dispatches stand on.  Record i's u64 key
+    (its pid_tgid) lies at keys + offset + i * stride.  Returns (perm, seg,
+    nseg): perm[0:n] the record indices sorted by key, a key's records in
+    record order; seg[0:nseg + 1] the start of each key's run in perm, with
+    seg[nseg] = n.  Invalid input (n == 0, no keys, stride % 8) raises with
+    the hipError_t."""
+    if keys is not None and n and stride > 0 and offset + (n - 1) * stride + 8 > keys.nbytes:
+        raise ValueError(f"{n} keys at stride {stride} + {offset} do not fit {keys.nbytes} bytes")
+    scratch = DeviceBuffer(max(lib().bpftime_amd_group_scratch_bytes(n), 256))
+    perm, seg, nseg = C.c_void_p(), C.c_void_p(), C.c_uint64(0)
+    e = lib().bpftime_amd_group_threads(C.c_void_p(keys.ptr + offset) if keys is not None else None, stride, n,
+                                        C.c_void_p(scratch.ptr), C.byref(perm), C.byref(seg), C.byref(nseg), None)
+    if e:
+        raise EbpfError(f"group_threads failed: hipError_t {e}")
+    if not 0 < nseg.value <= n:
+        raise EbpfError(f"group_threads: {nseg.value} segments over {n} records")
+    return (scratch.download(np.uint32, n, perm.value - scratch.ptr),
+            scratch.download(np.uint32, nseg.value + 1, seg.value - scratch.ptr), nseg.value)
+
+
 def syscall_attach(prog_fd: int, sys_nr: int, enter: bool = True) -> int:
     """A program on the sys_enter / sys_exit tracepoint of sys_nr (-1: every
     syscall; syscall_trace_attach_impl.cpp:121-166): the attach id."""

@@ -17,19 +17,22 @@ FUNCS = (F0, F1, F2, F3, F4)
 # no environment variable steers runs its callbacks in the asm tier
 ASM_THREADS = 65536
 LDS_STACK = 64                                          # common.hpp kLdsStackMax
+# (threads, ragged's calls range) of the many-wave cases: the cut-off from both sides
+MANY_WAVES = [(4096, (1, 6)), (ASM_THREADS, (1, 3)), (ASM_THREADS + 1, (1, 3))]
 
 
 def auto_tier(threads):
     return 1 if threads <= ASM_THREADS else 0
 
 
-def ragged(threads, seed=5, funcs=FUNCS + (um.NOBODY,)):
-    """um.records' fields for `threads` recorded threads of 1-5 calls each (a
-    fixed seed; the calls of all threads interleaved at random, so a lane's
-    walk is ragged against its neighbours').  pid_tgid and strictly increasing
-    clocks as ut.records has them."""
+def ragged(threads, seed=5, funcs=FUNCS + (um.NOBODY,), calls=(1, 6)):
+    """um.records' fields for `threads` recorded threads of calls[0] ..
+    calls[1] - 1 calls each (1-5 by default; a fixed seed; the calls of all
+    threads interleaved at random, so a lane's walk is ragged against its
+    neighbours').  pid_tgid and strictly increasing clocks as ut.records has
+    them."""
     rng = np.random.default_rng(seed + 7 * threads)
-    calls = rng.integers(1, 6, threads)
+    calls = rng.integers(calls[0], calls[1], threads)
     owner = rng.permutation(np.repeat(np.arange(threads), calls))
     n = len(owner)
     r = um.records(n, seed=seed + threads, funcs=funcs)

@@ -33,27 +33,9 @@ from bpftime_amd import isa, gen, programs
 from bpftime_amd.isa import Asm
 
 from _helpers import make_maps
+from _syscall_threads import ARRAY, HASH, TRACEPOINT, attach as _attach, syscount as _syscount
 
 pytestmark = pytest.mark.gpu
-
-TRACEPOINT = 5  # BPF_PROG_TYPE_TRACEPOINT
-HASH, ARRAY = isa.BPF_MAP_TYPE_HASH, isa.BPF_MAP_TYPE_ARRAY
-
-
-def _attach(dev, o, code, nr, enter):
-    dev.syscall_attach(dev.prog_create(code, "p", TRACEPOINT), nr, enter)
-    o.attach(code, nr, enter)
-
-
-def _syscount(po, dev, **opts):
-    (ostart, odata, oro), (dstart, ddata, dro) = make_maps(
-        [(HASH, 4, 8, 10240), (HASH, 4, 32, 10240), (ARRAY, 4, programs.SYSCOUNT_RODATA, 1)], po, dev)
-    ro = programs.syscount_rodata(measure_latency=True, **opts)
-    assert oro.update(b"\0" * 4, ro) == 0 and dro.update(b"\0" * 4, ro) == 0
-    o = po.OracleSyscallDispatch()
-    _attach(dev, o, programs.syscount_enter(dstart.fd, dro.fd), -1, True)
-    _attach(dev, o, programs.syscount_exit(ddata.fd, dro.fd, dstart.fd), -1, False)
-    return o, (ostart, odata), (dstart, ddata)
 
 
 @pytest.mark.parametrize("filter_pid", [0, 1003])

@@ -10,7 +10,9 @@ other's.
 
 A block of the replay kernel is one wave, so the shapes are 1, 63, 64, 65 and
 130 recorded threads of 1-5 calls each: a lone lane, a wave short of a lane, a
-full wave, a wave and a lane, three blocks with a ragged last one.  Hash maps
+full wave, a wave and a lane, three blocks with a ragged last one; and, for
+funclatency's pair beside tagging probes, 4,096, 65,536 and 65,537 threads:
+many waves, and the automatic cut-off (ua.ASM_THREADS) from both sides.  Hash maps
 hold at least twice their distinct keys and the counting programs insert 0,
 look up and add (programs._count_key_r0), so no insert races for a last
 slot."""
@@ -44,8 +46,10 @@ def buf(a):
 class Bench:
     """Device and model side by side: attach a (code, callable) pair to both."""
 
-    def __init__(self):
-        self.model, self.n, self.snaps = ue.EventModel(), 0, []
+    def __init__(self, bulk=False):
+        """bulk: snapshot() reads a hash map back whole (Map.hash_items), not
+        key by key: for maps of many thousand entries."""
+        self.model, self.n, self.snaps, self.bulk = ue.EventModel(), 0, [], bulk
 
     def attach(self, pair, func, kind=dev.UPROBE, cookie=None):
         self.n += 1
@@ -54,8 +58,15 @@ class Bench:
         return dev.uprobe_attach(fd, func, kind, cookie)
 
     # a device map beside the model's container: snapshot() holds one against the other
+    def _whole(self, m, d):
+        ints = lambda kv: {int.from_bytes(k, "little"): int.from_bytes(v, "little") for k, v in kv.items()}  # noqa: E731
+        self.snaps.append(lambda: (ints(m.hash_items()), m.count(), d, len(d)))
+        return m, d
+
     def u32_hash(self, entries, keys):
         m, d = dev.Map(HASH, 4, 8, entries), {}
+        if self.bulk:
+            return self._whole(m, d)
         self.snaps.append(lambda: ({k: int.from_bytes(v, "little") for k in keys
                                     if (v := m.lookup(int(k).to_bytes(4, "little"))) is not None}, m.count(),
                                    d, len(d)))
@@ -63,6 +74,8 @@ class Bench:
 
     def u64_hash(self, entries):
         m, d = dev.Map(HASH, 8, 8, entries), {}
+        if self.bulk:
+            return self._whole(m, d)
         self.snaps.append(lambda: (um.hash_counts(m, d.keys()), m.count(), d, len(d)))
         return m, d
 
@@ -114,7 +127,7 @@ def dispatch(b, r, events=None, flags=THREADS, pid=True, clock=True):
     return got, list(st), list(rets)
 
 
-def three_ways(monkeypatch, setup, run, tiers):
+def three_ways(monkeypatch, setup, run, tiers, bulk=False):
     """setup(b) attaches to a fresh Bench on a fresh runtime; run(b) dispatches
     and returns what to compare; once per mode, the tier asserted after each."""
     seen = []
@@ -125,7 +138,7 @@ def three_ways(monkeypatch, setup, run, tiers):
             monkeypatch.delenv("BPFTIME_AMD_SEQ_ASM", raising=False)
         else:
             monkeypatch.setenv("BPFTIME_AMD_SEQ_ASM", mode)
-        b = Bench()
+        b = Bench(bulk)
         setup(b)
         got = run(b)
         assert dev.last_seq_tier() == tier, f"BPFTIME_AMD_SEQ_ASM={mode}"
@@ -171,6 +184,67 @@ def test_per_thread_state_and_mixed_program_masks(fresh_runtime, monkeypatch, th
     tiers = [ua.auto_tier(threads), 1, 0] if tag == "di" else [0, 0, 0]
     failed, _, _ = three_ways(monkeypatch, setup, lambda b: dispatch(b, r, ev), tiers)
     assert failed == 0 and sum(hists[0]) == int((r["func"] == F1).sum())
+
+
+# Many waves, and the automatic cut-off from both sides: 4,096 threads of 1-5
+# calls, then ua.ASM_THREADS (the last count the library puts in the asm tier)
+# and ua.ASM_THREADS + 1 (the first it puts in the C++ tier; the last one-wave
+# block holds one lane) of 1-2 calls each
+MANY = ua.MANY_WAVES
+_many = {}
+
+
+def many_records(threads, calls):
+    """ua.ragged for the many-wave cases, built once per shape (read-only)."""
+    if threads not in _many:
+        _many[threads] = ua.ragged(threads, calls=calls)
+        assert len(np.unique(_many[threads]["pid"])) == threads
+    return _many[threads]
+
+
+@pytest.mark.parametrize("events", [False, True], ids=["calls", "flat-events"])
+@pytest.mark.parametrize("threads,calls", MANY, ids=[str(t) for t, _ in MANY])
+def test_many_waves_and_the_cut_off_from_both_sides(fresh_runtime, monkeypatch, threads, calls, events):
+    """The "di" arm of test_per_thread_state_and_mixed_program_masks at 4,096,
+    65,536 and 65,537 threads: funclatency's pair on F1 beside di_count tags
+    on F2, by the call dispatch and by the flat event list, three ways.  Every
+    wave inserts into starts[tid] at once; past the cut-off the forced asm
+    tier is the contended regime.  The maps are read back whole."""
+    r = many_records(threads, calls)
+    hists = []
+
+    def setup(b):
+        hists.append(funclat(b, r, F1))
+        (mc, cookies), (mi, ips) = b.u64_hash(2 * len(r["func"]) + 16), b.u64_hash(16)
+        b.attach(ut.di_count(mc.fd, cookies), F2)
+        b.attach(ut.di_count(mi.fd, ips), F2)
+        b.attach(ut.di_count(mc.fd, cookies), F1, dev.URETPROBE)
+    ev = ue.flat_events(len(r["func"])) if events else None
+    tiers = [ua.auto_tier(threads), 1, 0]
+    assert tiers[0] == (1 if threads <= 65536 else 0)
+    failed, _, _ = three_ways(monkeypatch, setup, lambda b: dispatch(b, r, ev), tiers, bulk=True)
+    assert failed == 0 and sum(hists[0]) == int((r["func"] == F1).sum()) > threads // 8
+
+
+def test_nested_calls_over_many_waves(fresh_runtime, monkeypatch):
+    """test_mixed_phase_waves' nested event lists (entry / inner entry / inner
+    return / return, recursion, up to four deep) at 4,096 threads against
+    EventModel: thread 0 walks about half the events, the upper half of the
+    threads one call each."""
+    threads = 4096
+    r = ue.traces(3 * threads, threads, max_depth=4)
+    assert len(set(r["owner"])) == threads == len(np.unique(r["pid"])) and 2 <= ue.depth_profile(r) <= 4
+    bys = []
+
+    def setup(b):
+        funclat(b, r, F1, delete=True)
+        (md, depth), (mb, by) = b.u32_hash(2 * threads + 8, tids(r)), b.hist(ue.SLOTS)
+        for f in (F0, F1):
+            b.attach(ue.depth_entry(md.fd, mb.fd, depth, by), f)
+            b.attach(ue.depth_return(md.fd, depth), f, dev.URETPROBE)
+        bys.append(by)
+    failed, _, _ = three_ways(monkeypatch, setup, lambda b: dispatch(b, r, r["events"]), [1, 1, 0], bulk=True)
+    assert failed == 0 and sum(bys[0][1:]) > 0           # calls that began inside another probed call
 
 
 @pytest.mark.parametrize("threads", [64, 65, 130])
