@@ -22,7 +22,7 @@ constexpr uint32_t kBlock = 256;        // threads per workgroup (4 waves)
 constexpr uint32_t kDbgXlat = 1u << 30;
 constexpr uint32_t kLdsStackMax = 64;   // per-lane stack bytes kept in LDS
 constexpr uint32_t kComb = 256;         // per-block LDS combining entries (counter adds), minimum
-constexpr uint32_t kCombMax = 4096;     // ... and maximum (a multiple of 8 in between, vm_api.cpp)
+constexpr uint32_t kCombMax = 4096;     // ... and maximum (a multiple of 8 in between, vm_plan.cpp)
 constexpr uint32_t kMissParts = 256;    // miss-log partitions (KParams::miss_log)
 
 // Internal (pre-decoded) opcodes.  The device switch dispatches on these; the
@@ -344,7 +344,7 @@ constexpr uint32_t kLruScan = 256;             // parallel batches: buckets exam
 // bpf_tail_call (helper 12, bpf_helper.cpp:568-650).  The reference runs the
 // target as a nested exec over a 64-B copy of the ctx and returns its r0 to
 // the caller (depth <= 32).  Here the caller and every program a PROG_ARRAY
-// can name are linked into one image at launch (vm_api.cpp), the targets'
+// can name are linked into one image at launch (vm_image.cpp), the targets'
 // exits become calls of kRetHelper, and a call pushes a per-lane frame
 // {r1..r10, return pc, ctx bytes, stack bytes} that the matching return pops:
 // the callee runs on the same stack and ctx, restored afterwards, which is
@@ -372,7 +372,7 @@ constexpr uint32_t kFrameRematShift = 50;
 // (after the combining table): w = 0 the header (as word 11; 0 = the frame is
 // in global memory, a full frame the C++ tier pushed), then the live
 // registers in order, the ctx words of the ctx mask, the stack words of the
-// stack mask (vm_api.cpp sizes words = 1 + the most live registers of a tail
+// stack mask (vm_plan.cpp sizes words = 1 + the most live registers of a tail
 // call + both masks' words, and the depths to keep the block's residency)
 constexpr uint32_t kTailLdsMax = 4;  // depths held in LDS at most
 
@@ -424,7 +424,7 @@ struct KParams {
   const DInsn *prog;
   const FInsn *fast;      // threaded-code form for the asm fast path
   uint32_t fast_div;      // lane groups (divergence) may be scheduled in asm
-  uint32_t comb_entries;  // LDS combining entries per block (0: none; sized per launch, vm_api.cpp)
+  uint32_t comb_entries;  // LDS combining entries per block (0: none; sized per launch, vm_plan.cpp)
   const DMap *maps;
   uint8_t *data;          // base of unit slots (device)
   const uint32_t *lens;   // per-unit lengths or nullptr
@@ -479,7 +479,7 @@ struct KParams {
   uint64_t *miss_log;        // combining-table misses: [grid][kMissParts][miss_cap] {tag, delta} records, or nullptr
   uint32_t *miss_counts;     // [grid][kMissParts] records each block wrote (k_miss_merge reads them)
   uint32_t miss_cap;         // records per block and partition (even)
-  const int32_t *tail_slots; // images: per PROG_ARRAY fd the offset of its slots' entry pcs, then those (vm_api.cpp)
+  const int32_t *tail_slots; // images: per PROG_ARRAY fd the offset of its slots' entry pcs, then those (vm_image.cpp)
   // syscall dispatch state (include/ebpf-vm.h struct ebpf_batch): per unit
   // override flags and return value, the phase bit (1 enter, 2 exit), or null
   uint32_t *sys_state;
@@ -562,7 +562,7 @@ constexpr uint32_t kSeqMaxProgs = 64;  // attached programs a thread-ordered dis
 // CALL_REC handler (loader.cpp link_fast rec)
 constexpr uint32_t kSeqPidOff = 64, kSeqClockOff = 72, kSeqCtxWords = 10;
 // threads up to which the thread-ordered dispatch runs its callbacks in the
-// asm tier (vm_api.cpp seq_dispatch)
+// asm tier (vm_seq.cpp seq_dispatch)
 constexpr uint64_t kSeqAsmThreads = 16384;
 // Where a thread-ordered kernel keeps a callback's caller and clock, as byte
 // offsets from the lane's ctx copy (loader.cpp link_fast: the CALL_REC links'
@@ -635,7 +635,7 @@ constexpr uint32_t kUpSeqBlock = 64;
 constexpr uint32_t kUpSeqPidOff = 168, kUpSeqClockOff = 176, kUpSeqCtxWords = 23;
 constexpr RecOffs kUpSeqRecOffs{kUpSeqPidOff, kUpSeqClockOff};
 // threads up to which the thread-ordered uprobe replay runs its callbacks in
-// the asm tier (vm_api.cpp useq_dispatch): the largest count measured, where
+// the asm tier (vm_seq.cpp useq_dispatch): the largest count measured, where
 // the asm tier still led (profiles/uprobe_asm_measurement.txt)
 constexpr uint64_t kUpSeqAsmThreads = 65536;
 struct UpSeqParams {
@@ -757,13 +757,13 @@ inline size_t seq_lds_bytes(uint32_t block, bool fast) {
 // the tail-call constants (gen_fast.py lcache_probe; the lookup's FInsn w4
 // carries the set count).  A slot found for a key stays that key's slot for
 // the rest of a launch when nothing deletes.
-constexpr uint32_t kLcacheSets = 1024;  // default set count (BPFTIME_AMD_LCACHE_SETS: vm_api.cpp lcache_sets)
+constexpr uint32_t kLcacheSets = 1024;  // default set count (BPFTIME_AMD_LCACHE_SETS: loader.cpp lcache_sets)
 BA_HD inline size_t lcache_bytes(uint32_t sets) { return (size_t)(32 + 8) * sets; }
 // ... and after the table, the LDS tail-call frames of an XDP image
 // (tail_lds: depths | words per frame << 8; [depth][word][lane] u64)
 BA_HD constexpr uint32_t tail_lds_lane_bytes(uint32_t tail_lds) { return (tail_lds & 0xff) * (tail_lds >> 8) * 8; }
 // Per-lane LDS areas (the XDP ctx, the stack) at a lane stride of 8 x an odd
-// number of bytes (BPFTIME_AMD_LANE_PAD=1; off by default, vm_api.cpp
+// number of bytes (BPFTIME_AMD_LANE_PAD=1; off by default, vm_plan.cpp
 // lane_pad): the same offset in 16 lanes' areas then falls on 16 different
 // bank pairs (dword d of lane t at bank (stride / 4 * t + d) mod 32, stride
 // / 4 = 2 x odd), where a power-of-two stride puts every fourth lane on one

@@ -599,7 +599,7 @@ __device__ uint64_t lpm_lookup(const DMap &m, uint64_t key) {
 }
 
 // Program-side LPM trie writes, ORDERED batches only (one lane runs the
-// units in order; vm_api.cpp refuses other batches of such programs):
+// units in order; vm_upkeep.cpp refuses other batches of such programs):
 // lpm_trie_map.cpp:266-488 (elem_update) and :490-541 (elem_delete, a
 // logical deletion: the node becomes intermediate) restated over the
 // replica exactly as the host's LpmTrie::update / remove (lpm_trie.hpp) do over
@@ -1247,7 +1247,7 @@ __device__ __noinline__ uint64_t helper_bloom(const DMap *maps, uint64_t fd, uin
 // element with ticket t lives in slot t % max_entries; count = tail - head.
 //
 // A parallel launch sees one kind of access per map (the loader's call-site
-// analysis and vm_api.cpp's launch check: add-only, remove-only or peek-only),
+// analysis and vm_upkeep.cpp's launch check: add-only, remove-only or peek-only),
 // so only one end moves while it runs and nothing reads a slot that a push of
 // the same launch claimed.  The calling lanes of a wave that name the same
 // map form a group; its first lane claims `take` tickets for all of them with

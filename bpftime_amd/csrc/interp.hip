@@ -852,7 +852,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(4))) void k_
   const uint32_t chain_bits = (KIND != CTX_XDP ? 8u : 0u) | (KIND == CTX_RAW ? 16u : 0u) | (p.lens ? 32u : 0u) |
                               (KIND == CTX_SYSCALL ? 64u : 0u) | (IMAGE ? 128u : 0u) |
                               (p.step_cpu << 16);
-  // the host linker's query (vm_api.cpp fast_xlat, one unit): the asm block
+  // the host linker's query (vm_image.cpp fast_xlat, one unit): the asm block
   // writes its handlers' offsets (u32 per handler id) at p.verdicts and the
   // kernel ends (through the one run_fast site, so the block is not inlined
   // twice)
@@ -1066,7 +1066,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(4))) void k_
           // frames word-interleaved across the grid's lanes ([depth][word][lane]):
           // a wave's save of one word is one coalesced 512-B store
           uint64_t *const fbase = (uint64_t *)p.frames + (blockIdx.x * kBlock + tid);
-          const uint64_t kLanes = (uint64_t)gridDim.x * kBlock;  // frames sized for this launch (vm_api.cpp)
+          const uint64_t kLanes = (uint64_t)gridDim.x * kBlock;  // frames sized for this launch (vm_exec.cpp)
           auto FW = [&](uint32_t d, uint32_t w) -> uint64_t & {
             return fbase[((uint64_t)d * p.frame_words + w) * kLanes];
           };
@@ -1428,7 +1428,7 @@ __global__ __launch_bounds__(kBigBlock) void k_miss_merge(const uint64_t *log, c
 }
 
 // Thread-ordered syscall dispatch (common.hpp SeqParams; the host side is
-// syscall_dispatch.cpp / vm_api.cpp seq_dispatch).  dispatch_syscall
+// syscall_dispatch.cpp / vm_seq.cpp seq_dispatch).  dispatch_syscall
 // (attach/syscall_trace_attach_impl/src/syscall_trace_attach_impl.cpp:18-95)
 // runs a call's callbacks on the calling thread, one call after another:
 // here lane t walks thread t's records in record order and, per record, runs
@@ -1755,7 +1755,7 @@ extern "C" int bpftime_amd_seq_prof(unsigned long long *out, int reset) {
 #endif
 
 // Thread-ordered uprobe replay (common.hpp UpSeqParams; the host side is
-// uprobe_dispatch.cpp / vm_api.cpp useq_dispatch).  The reference runs a
+// uprobe_dispatch.cpp / vm_seq.cpp useq_dispatch).  The reference runs a
 // call's callbacks on the calling thread (frida_internal_attach_entry.cpp:
 // 221-239: the function's uprobes at entry, its uretprobes at return, in
 // attach order; the override handler :243-277; a replace returns r0,
@@ -1775,7 +1775,7 @@ extern "C" int bpftime_amd_seq_prof(unsigned long long *out, int reset) {
 // and every instruction the asm leaves -- 58 / 187 and the map helpers among
 // them -- takes the same C++ step and helper path either way.  (173 / 174: the
 // loader marks their callers for the scratch-stack kernels, and the host keeps
-// a dispatch with such a program in the C++ tier, vm_api.cpp useq_dispatch.)
+// a dispatch with such a program in the C++ tier, vm_seq.cpp useq_dispatch.)
 //
 // kEvents (bpftime_amd_uprobe_dispatch_events): the walked words are events,
 // (record << 1) | phase, in the thread's recorded order, so a nested or

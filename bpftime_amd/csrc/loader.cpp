@@ -506,7 +506,7 @@ int load_program(const RawInsn *code, size_t n, const std::map<size_t, size_t> &
   for (size_t i = 0; i < n; i++) {
     RawInsn &cur = in[i];
     if (cur.code == 0x85 && cur.imm == kRetHelper && !entries.empty()) {
-      // linked image (vm_api.cpp link_tail_image): a target's exit
+      // linked image (vm_image.cpp link_tail_image): a target's exit
     } else if (cur.code == 0x85) {
       if (cur.imm == (int32_t)kTailHelper) out.tail_call = true;
       if (helper_id_map.find((size_t)(uint32_t)cur.imm) == helper_id_map.end() || cur.imm < 0) {
@@ -864,7 +864,7 @@ static bool is_cond_jump(uint8_t op) { return op >= X_JEQ && op <= X_JSLE; }
 // in[i][r]: kind of register r before instruction i; returns false when the
 // program may rewrite its ctx (then no ctx / packet kinds are trusted).
 //
-// A linked tail-call image (vm_api.cpp) also enters at every target: with r1
+// A linked tail-call image (vm_image.cpp) also enters at every target: with r1
 // = the ctx the caller passed (`ctx_entries`: the caller's own ctx / slot at
 // every tail-call site, checked by the caller of this function), r2 = 64, r10
 // = the same stack top.  Only stores that can move the packet pointers (ctx
@@ -1458,7 +1458,7 @@ static void qs_call_sites(const std::vector<DInsn> &p, const std::vector<uint8_t
 // The ctx and stack words a linked target may write (FastForm
 // tail_ctx_mask / tail_stack_mask): its stores through ctx / stack pointers
 // of known offset, and the helpers that write ctx fields or stack buffers.
-// Targets are the pcs before the loaded program (vm_api.cpp links them first,
+// Targets are the pcs before the loaded program (vm_image.cpp links them first,
 // behind a jump at pc 0); anything not understood saves everything.
 static void tail_save_masks(const std::vector<DInsn> &p, const std::vector<std::vector<PVal>> &in,
                             uint32_t stack_size, FastForm &out) {
@@ -1682,7 +1682,7 @@ static void map_effects(const std::vector<DInsn> &prog, const std::vector<std::v
           case kRetHelper: break;  // a linked target's exit
           case 12:
             // bpf_tail_call: nothing of its own.  What the targets do is in
-            // the linked image (vm_api.cpp link_tail_image_locked), which this
+            // the linked image (vm_image.cpp link_tail_image_locked), which this
             // pass sees whole; the dispatches ask for the effects of that
             // image (vm_map_effects) and send tail calls to no other plan
             break;
@@ -1719,7 +1719,7 @@ static void map_effects(const std::vector<DInsn> &prog, const std::vector<std::v
             // the serial run does (the claim keys of helper_stackid and
             // stack_commit.hip; launches with BPF_F_REUSE_STACKID or a
             // program-side lookup / delete are refused outside ORDERED,
-            // vm_api.cpp st_launch_check; tests/test_gpu_stacktrace.py
+            // vm_upkeep.cpp st_launch_check; tests/test_gpu_stacktrace.py
             // test_parallel_matches_the_serial_model holds ids, -EEXIST
             // returns and slots against the serial model), so like a NOEXIST
             // insert it is no write the program conflicts with itself on
@@ -2217,7 +2217,7 @@ void link_fast(const FastForm &f, uint32_t head, uint32_t stage, bool ordered, c
         const bool staged = pid_off % 4 == 0 && pid_off + 8 <= stage;
         out[i].imm = staged ? (int64_t)(pid_off / 4) | (1ll << 32) : 0;
       }
-  // the launch's lookup-cache set count (vm_api.cpp) into the lookups that
+  // the launch's lookup-cache set count (vm_plan.cpp) into the lookups that
   // use it; a launch without a cache (0: the thread-ordered kernel) turns it off
   for (FInsn &x : out)
     if (x.w1 & FW_LCACHE) {

@@ -62,7 +62,7 @@ struct FastForm {
   uint32_t tail_max_live = 9;  // the most registers a tail call's frame keeps (FInsn imm popcount)
   // map_update_elem (2) / map_delete_elem (3) call sites that may reach an
   // LPM trie: {helper id, map fd}.  The device changes a trie only in ORDERED
-  // batches (dev_helpers.hpp lpm_update); vm_api.cpp refuses other batches
+  // batches (dev_helpers.hpp lpm_update); vm_upkeep.cpp refuses other batches
   std::vector<std::pair<uint32_t, int32_t>> lpm_writes;
   bool names_lpm = false;  // an lddw names an LPM trie (its launches take the LPM launch lock)
   // call sites that may reach a QUEUE / STACK map: helpers 87 / 88 / 89 and
@@ -70,7 +70,7 @@ struct FastForm {
   // cannot resolve it (helpers 1 / 2 / 3 then stand for every QUEUE / STACK
   // the program names in an lddw, one site each).  flags0: a push (87 / 2)
   // whose flags register is proven 0.  A parallel launch needs every such map
-  // add-only, remove-only or peek-only (vm_api.cpp qs_launch_check)
+  // add-only, remove-only or peek-only (vm_upkeep.cpp qs_launch_check)
   struct QsSite {
     uint32_t helper;
     int32_t fd;
@@ -81,7 +81,7 @@ struct FastForm {
   // in r2) and helpers 1 / 2 / 3 (r1), resolved as QsSite::fd is.  flags_ok: a
   // 27 whose flags register (r3) is a proven constant with BPF_F_REUSE_STACKID
   // clear.  A parallel launch needs every 27 site flags_ok and no 1 / 3 site
-  // (vm_api.cpp st_launch_check); 27 sites name the maps k_stack_commit visits
+  // (vm_upkeep.cpp st_launch_check); 27 sites name the maps k_stack_commit visits
   struct StSite {
     uint32_t helper;
     int32_t fd;
@@ -90,7 +90,7 @@ struct FastForm {
   std::vector<StSite> st_sites;
   // the ARRAY_OF_MAPS maps the program names in an lddw.  The inner maps a
   // lookup on one yields are named by no lddw: before a launch the host walks
-  // the slots of these maps (vm_api.cpp inner_launch_check)
+  // the slots of these maps (vm_upkeep.cpp inner_launch_check)
   std::vector<int32_t> outer_maps;
   // a store may reach the unit r1 points to at entry (the pointer kinds
   // cannot place every store on the stack, a map value or a constant)

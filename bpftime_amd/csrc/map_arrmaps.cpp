@@ -6,7 +6,7 @@
 // which it hands to the next map helper as r1.  bpf_map_attr has no
 // inner_map_fd and the reference ignores one (bpftime_shm_internal.cpp:889),
 // so the slots are untyped: any int may be stored, and what a slot names is
-// looked at only when a program is launched (vm_api.cpp inner_launch_check).
+// looked at only when a program is launched (vm_upkeep.cpp inner_launch_check).
 //
 // The slots in the arena are the only copy the device reads.  MapRec::
 // inner_slots mirrors them on the host for the launch walk; every host write

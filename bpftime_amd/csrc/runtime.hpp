@@ -37,7 +37,7 @@ struct MapRec {
   // (ENOMEM) until bpftime_amd_map_ack_error
   bool lpm_pool_out = false;
   // ARRAY_OF_MAPS: the host's copy of the slots (map_arrmaps.cpp keeps it equal
-  // to the arena's).  The launch walk (vm_api.cpp inner_launch_check) reads the
+  // to the arena's).  The launch walk (vm_upkeep.cpp inner_launch_check) reads the
   // inner fds here, never from device memory
   // (PERF_EVENT_ARRAY: the same mirror of its perf event fds, map_perfarr.cpp)
   std::vector<int32_t> inner_slots;
@@ -147,16 +147,16 @@ struct Runtime {
   // lookup cache (a found slot is trusted for the rest of the launch), one of
   // a program that can delete.  A cached launch never overlaps a deletion
   // (a program's, on any stream, or the host's): whichever comes second
-  // waits for the device first (vm_api.cpp exec_batch, map_hash.cpp hash_erase)
+  // waits for the device first (vm_upkeep.cpp LaunchUpkeep, map_hash.cpp hash_erase)
   std::atomic<bool> lcache_inflight{false}, deleter_inflight{false};
-  // LPM tries (vm_api.cpp exec_batch): launches of a runtime holding any are
+  // LPM tries (vm_upkeep.cpp LaunchUpkeep): launches of a runtime holding any are
   // prepared and launched under lpm_launch_mu; a launch that may write a
   // trie (ORDERED) waits for every launch that may still touch one, and any
   // launch after a writer waits for it
   std::mutex lpm_launch_mu;
   std::atomic<int> lpm_maps{0};
   std::atomic<bool> lpm_inflight{false}, lpm_writer_inflight{false};
-  // QUEUE / STACK maps (vm_api.cpp qs_launch_check): launches that may still
+  // QUEUE / STACK maps (vm_upkeep.cpp qs_launch_check): launches that may still
   // run and add to one / remove from or peek one.  A launch that removes from
   // or peeks a map never overlaps one that adds to a map, on any stream:
   // whichever comes second waits for the device first.  An ORDERED launch
@@ -185,7 +185,7 @@ void set_error(const std::string &e);
 __attribute__((visibility("hidden"))) int alloc_fd(int fd);
 
 // What the syscall dispatch needs to know of a loaded VM's program
-// (vm_api.cpp): bit 0 it calls bpf_override_return / bpf_set_retval (58 /
+// (vm_seq.cpp): bit 0 it calls bpf_override_return / bpf_set_retval (58 /
 // 187), bit 1 it may store into the memory r1 points to (its unit: the
 // dispatch then runs it on a copy of the records), bit 2 it calls
 // bpf_get_stackid / bpf_get_stack (27 / 67).  -1: no program loaded.

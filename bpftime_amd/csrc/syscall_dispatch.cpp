@@ -29,7 +29,7 @@
 //  * thread-ordered: records grouped by their recorded thread (group.hip),
 //    one lane per thread walking its records in record order, each record's
 //    callbacks run back to back as dispatch_syscall runs them (interp.hip
-//    k_sys_seq; vm_api.cpp seq_dispatch) -- the reference's schedule.
+//    k_sys_seq; vm_seq.cpp seq_dispatch) -- the reference's schedule.
 // The dispatch takes thread-ordered when two attachments may not commute
 // (the loader's map effects, loader.hpp FastForm::map_fx): one writes a map
 // the other reads or writes, or adds to a map the other reads.  syscount's

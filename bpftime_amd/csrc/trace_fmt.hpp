@@ -1,6 +1,6 @@
 // bpftime_amd: bpf_trace_printk's format scanner, the record a call leaves in
 // the device log, and the host formatter that turns a record into the line
-// snprintf would print (dev_helpers.hpp helper_trace, vm_api.cpp
+// snprintf would print (dev_helpers.hpp helper_trace, vm_abi.cpp
 // bpftime_amd_trace_read).  The scanner is plain C++ over a byte getter, so
 // the device helper (bytes the range guard admitted) and the host formatter
 // (the record's copy) run the same code (tests/cpp/trace_fmt_test.cpp).

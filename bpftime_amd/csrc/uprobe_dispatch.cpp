@@ -26,7 +26,7 @@
 //  * thread-ordered (BPFTIME_AMD_DISPATCH_THREADS): the records grouped by
 //    their recorded thread (group.hip), one lane per thread walking its calls
 //    in record order, each call's entry callbacks and then its return
-//    callbacks back to back (interp.hip k_up_seq; vm_api.cpp useq_dispatch) --
+//    callbacks back to back (interp.hip k_up_seq; vm_seq.cpp useq_dispatch) --
 //    the reference's schedule, whatever the programs share.  funclatency's
 //    pair is the case (example/tracing/funclatency/funclatency.bpf.c: the
 //    entry probe stores starts[tid], the return probe reads it).  The plan is
@@ -250,7 +250,7 @@ int attach(int prog_fd, uint64_t func, int kind, const uint64_t *cookie, int lin
   return g_next_id++;
 }
 
-// ebpf_batch's rules for the stack fields (vm_api.cpp exec_batch), checked
+// ebpf_batch's rules for the stack fields (vm_exec.cpp exec_batch), checked
 // here so that a dispatch is refused before its first launch
 std::string stack_fields_bad(const struct bpftime_amd_call_records *r) {
   if (!r->stack_arr) return "";
@@ -397,7 +397,7 @@ int64_t run_one(const Attach &a, bool at_entry, const struct bpftime_amd_call_re
 }
 
 // The thread-ordered plan: group the records by caller, one launch for every
-// attachment (vm_api.cpp useq_dispatch).  >= 0 failed callbacks (SYNC), -1 error.
+// attachment (vm_seq.cpp useq_dispatch).  >= 0 failed callbacks (SYNC), -1 error.
 // With `events` (n_events words (record << 1) | phase) the walked items are the
 // events: they are grouped by their record's caller (uprobe_dispatch.hip
 // k_ug_event_keys, which also counts the events naming no record; the count

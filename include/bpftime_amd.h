@@ -912,7 +912,7 @@ size_t bpftime_amd_static_lds(uint32_t kind, bool big_stack, bool gregs, uint32_
 /* Dynamic + static LDS bytes of an interpreter block (ctx kind, 512-B scratch
  * stack, per-lane stack bytes, combining-table entries, lookup-cache sets,
  * ctx in LDS, register copy in global memory, lanes): a launch whose block
- * needs more than 160 KiB fails with a named error (vm_api.cpp). */
+ * needs more than 160 KiB fails with a named error (vm_upkeep.cpp). */
 size_t bpftime_amd_lds_bytes(uint32_t kind, bool big_stack, uint32_t stack_size, uint32_t comb_entries,
                              uint32_t lcache_sets, bool ctx_lds, bool gregs, uint32_t block);
 

@@ -113,7 +113,7 @@ def test_lds_sizing_of_launch_shapes():
     override shape that failed in round 4 (flow-hash with
     BPFTIME_AMD_COMB_ENTRIES=2000 BPFTIME_AMD_LCACHE_SETS=2048, 1024-lane
     blocks) exceeds the CU's 160 KiB and is refused by name before a launch
-    (vm_api.cpp lds_fit_error); the default flow-hash and headline shapes
+    (vm_upkeep.cpp lds_fit_error); the default flow-hash and headline shapes
     fit."""
     l = _lib.lib()
     cu = 160 * 1024

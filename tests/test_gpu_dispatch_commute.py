@@ -1,6 +1,6 @@
 """The syscall dispatch planner on the device against orc_sys_dispatch
 (csrc/syscall_dispatch.cpp plan_for / first_map_conflict, csrc/loader.cpp
-map_effects, csrc/vm_api.cpp seq_dispatch).
+map_effects, csrc/vm_seq.cpp seq_dispatch).
 
 For every case of tests/_dispatch_cases.py: the plan the rule gives it is the
 plan syscall_dispatch_plan() answers, and a dispatch with NO plan flag leaves

@@ -1,6 +1,6 @@
 """Direct dispatch of the asm tier (gen_fast.py): linked FInsns name their
 handlers by offset from the asm's handler base, which the host learns from
-one query launch per asm variant (vm_api.cpp fast_xlat).  Those offsets are
+one query launch per asm variant (vm_image.cpp fast_xlat).  Those offsets are
 assembly-time constants of the asm text, so every kernel instance that runs
 one variant must report the same table; this checks it over every instance a
 launch can select."""

@@ -5,7 +5,7 @@ mechanism, at a few thousand units, with the switch off and on, bit-exact
 against the oracle both times, and asserts through VM.last_launch() /
 VM.fast_handler that the switch changed what it claims to.
 
-BPFTIME_AMD_LANE_PAD is read once per process (a static in vm_api.cpp) and
+BPFTIME_AMD_LANE_PAD is read once per process (a static in vm_plan.cpp) and
 cannot be switched inside a test run: it is left out.  BPFTIME_AMD_NO_LPM_FLAT
 chooses how the host builds an LPM trie's device replica, which neither the
 launch info nor a handler shows: its case is parity-only.  The lookup cache's

@@ -1,4 +1,4 @@
-"""The thread-ordered syscall dispatch (k_sys_seq, vm_api.cpp seq_dispatch) at
+"""The thread-ordered syscall dispatch (k_sys_seq, vm_seq.cpp seq_dispatch) at
 many waves and on both sides of the automatic tier cut-off, bit-exact against
 the oracle's record-by-record dispatch_syscall (oracle/drivers.c
 orc_sys_dispatch): every element of `out`, every entry of every map and the

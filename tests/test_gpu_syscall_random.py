@@ -1,5 +1,5 @@
 """Random sys_enter / sys_exit program pairs that pass state from one to the
-other, through the thread-ordered dispatch (csrc/vm_api.cpp seq_dispatch,
+other, through the thread-ordered dispatch (csrc/vm_seq.cpp seq_dispatch,
 interp.hip k_sys_seq) in both of its tiers -- the asm tier (LDS stacks,
 caller / clock beside the ctx copy, lane groups in asm) and the C++ tier
 (BPFTIME_AMD_SEQ_ASM=0) -- against the oracle's record-by-record

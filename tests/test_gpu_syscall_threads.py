@@ -65,7 +65,7 @@ def test_syscount_latency_pair_bit_exact(fresh_oracle, fresh_runtime, filter_pid
 @pytest.mark.parametrize("tier", ["asm", "cpp"])
 def test_syscount_pair_both_tiers(fresh_oracle, fresh_runtime, monkeypatch, tier):
     """The callbacks run in the asm tier when every stack fits the LDS stacks
-    (vm_api.cpp seq_dispatch), else -- or with BPFTIME_AMD_SEQ_ASM=0 -- in
+    (vm_seq.cpp seq_dispatch), else -- or with BPFTIME_AMD_SEQ_ASM=0 -- in
     the C++ tier: both bit-exact, over 256 threads."""
     po, dev = fresh_oracle, fresh_runtime
     monkeypatch.setenv("BPFTIME_AMD_SEQ_ASM", "1" if tier == "asm" else "0")

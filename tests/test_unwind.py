@@ -4,7 +4,7 @@ registered under that ubpf id which returns 0 ends the program with r0 = 0.
 The oracle restates it (oracle/interp.c, the 0x85 case); the device ends the
 unit in its C++ tier (interp.hip R_CALL), map_lookup_elem leaving its asm
 handlers when it is the unwind helper.  ubpf ids follow the registration
-order of the default helpers, the same on both sides (vm_api.cpp
+order of the default helpers, the same on both sides (vm_abi.cpp
 bpftime_amd_register_default_helpers, oracle/helpers.c)."""
 import struct
 
