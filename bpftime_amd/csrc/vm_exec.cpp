@@ -22,6 +22,10 @@ namespace {
 struct BatchFacts {
   uint32_t kind = CTX_RAW;  // the kernel's ctx kind
   bool uprobe = false, sys_exit = false, ordered = false;
+  // the initial data offset inside each slot.  A descriptor names its frame's
+  // first byte itself, so descriptor batches have none: ebpf_batch::head is not
+  // used there (include/ebpf-vm.h)
+  uint32_t head = 0;
 };
 
 // Every refusal that depends on the ebpf_batch alone ("": none), and the facts
@@ -41,6 +45,7 @@ std::string check_batch(const ebpf_batch *b, BatchFacts &f) {
   const bool sys_exit = f.sys_exit = b->ctx_kind == EBPF_CTX_SYSCALL_EXIT;
   const uint32_t kind = f.kind = sys_exit ? CTX_SYSCALL : uprobe ? CTX_RAW : b->ctx_kind;
   f.ordered = (b->flags & EBPF_BATCH_ORDERED) != 0;
+  f.head = b->descs ? 0 : b->head;
   if (b->sys_state && ((kind != CTX_SYSCALL && !uprobe) || (b->sys_phase != 1 && b->sys_phase != 2)))
     return uprobe ? "sys_state needs sys_phase 1 (enter) or 2 (exit)"
                   : "sys_state needs a syscall batch with sys_phase 1 (enter) or 2 (exit)";
@@ -189,7 +194,7 @@ void fill_params(Mi355xVm &vm, const ebpf_batch *b, const BatchFacts &f, const L
   p.unwind_idx = l.unwind_helper;
   p.ifindex = b->ingress_ifindex;
   p.rxq = b->rx_queue_index;
-  p.head = b->head;
+  p.head = f.head;
   p.checked = (b->flags & EBPF_BATCH_UNCHECKED) ? 0 : 1;
   if (im.d_tail_entry) {
     p.tail_entry = im.d_tail_entry;
@@ -233,7 +238,7 @@ PlanIn plan_in(const ebpf_batch *b, const BatchFacts &f, const Image &im, bool r
   in.tail_ctx_mask = im.fx.tail_ctx_mask;
   in.tail_stack_mask = im.fx.tail_stack_mask;
   in.rings = rings;
-  in.stage_need = stage_need(ff, xdp ? b->head : 0);
+  in.stage_need = stage_need(ff, xdp ? f.head : 0);
   // (descriptor batches: the kernel checks each wave's frames)
   in.aligned = ((uint64_t)(uintptr_t)b->data % 16) == 0 &&
                (b->descs ? true : (b->stride % 16) == 0 && b->stride >= in.stage_need);
@@ -428,7 +433,7 @@ int Mi355xVm::exec_batch(const ebpf_batch *b) {
         return bpftime_amd_occupancy(in.kind, in.big_stack, dyn, greg, block, in.tail && !in.big_stack);
       },
       device_cus);
-  p.fast = im.linked(pl.greg, xdp, xdp ? b->head : 0, pl.stage, f.ordered, l.unwind_helper, pl.lcache, b->pid_tgid_off);
+  p.fast = im.linked(pl.greg, xdp, xdp ? f.head : 0, pl.stage, f.ordered, l.unwind_helper, pl.lcache, b->pid_tgid_off);
   if (!p.fast) {
     error = "device upload failed";
     return -1;

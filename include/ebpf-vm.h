@@ -136,8 +136,17 @@ struct ebpf_batch {
 	/* AF_XDP descriptor mode (descs != NULL): `data` is a umem of umem_bytes,
 	 * unit i is the frame at data + descs[i].addr of descs[i].len bytes
 	 * (struct xdp_desc, linux/if_xdp.h), `stride` the umem chunk size
-	 * (ctx buffer_start / buffer_end = the frame's chunk); lens / fixed_len /
-	 * head are not used.  A descriptor outside the umem fails its unit. */
+	 * (ctx buffer_start / buffer_end = the frame's chunk; stride 0: the frame
+	 * itself, buffer_end = data_end).  data_off_out counts from the frame's
+	 * addr.  lens / fixed_len / head are not used: any values give the results
+	 * of a batch without them, and lens is not written.
+	 * A descriptor with addr >= umem_bytes or len > umem_bytes - addr (len the
+	 * 32-bit field; options is never read) is not run: its unit counts as
+	 * failed and gets verdict / ret 0, data_off_out 0 and len_out 0.
+	 * In contract: the frames of one batch do not overlap and no descriptor
+	 * appears twice, addr % stride + len <= stride (a frame stays inside its
+	 * chunk), and addresses are in aligned-chunk form.  Other placements are
+	 * not supported. */
 	const struct ebpf_xdp_desc *descs;
 	uint64_t umem_bytes;
 	int64_t sys_nr;          /* with EBPF_BATCH_SYS_NR: the syscall nr a per-syscall program is attached to */

@@ -135,6 +135,19 @@ def test_syscall_agg_parity(fresh_oracle, fresh_runtime):
     assert 60 not in counts and 231 not in counts
 
 
+def percpu_counter_prog(fd):
+    """counts[unit word & 3] += 1 in a PERCPU_ARRAY; r0 = the virtual CPU."""
+    a = Asm()
+    a.ldx(8, 6, 1, 0)                      # r6 = unit word
+    a.alu64("and", 6, 3).stx(4, 10, -4, "r6")
+    a.ld_map_fd(1, fd).mov64(2, "r10").add64(2, -4).call(1)
+    a.jmp("jeq", 0, 0, "out")
+    a.ldx(8, 1, 0, 0).add64(1, 1).stx(8, 0, 0, "r1")
+    a.call(isa.BPF_FUNC_get_smp_processor_id)
+    a.label("out").exit()
+    return a.assemble()
+
+
 def test_percpu_array_counter(fresh_oracle, fresh_runtime):
     """bpf_get_smp_processor_id + PERCPU_ARRAY: virtual CPU of unit i is
     (i // 64) % ncpu on both sides."""
@@ -143,15 +156,7 @@ def test_percpu_array_counter(fresh_oracle, fresh_runtime):
     po.set_ncpu(ncpu)
     dev.set_ncpu(ncpu)
     (om,), (dm,) = make_maps([(isa.BPF_MAP_TYPE_PERCPU_ARRAY, 4, 8, 4)], po, dev)
-    a = Asm()
-    a.ldx(8, 6, 1, 0)                      # r6 = unit word
-    a.alu64("and", 6, 3).stx(4, 10, -4, "r6")
-    a.ld_map_fd(1, dm.fd).mov64(2, "r10").add64(2, -4).call(1)
-    a.jmp("jeq", 0, 0, "out")
-    a.ldx(8, 1, 0, 0).add64(1, 1).stx(8, 0, 0, "r1")
-    a.call(isa.BPF_FUNC_get_smp_processor_id)
-    a.label("out").exit()
-    code = a.assemble()
+    code = percpu_counter_prog(dm.fd)
     n = 5000
     units = gen.sm64(8, np.arange(n, dtype=np.uint64)).view(np.uint8).reshape(n, 8)
     ovm = po.OracleVM()

@@ -301,15 +301,21 @@ def test_step_limit_stops_infinite_loop(fresh_runtime):
     assert vm.exec_batch(dev.CTX_RAW, d, 64, 8, fixed_len=8, rets=dr) == 64
 
 
+def last_writer_prog(fd):
+    """value = value + the unit's first word, by a plain load and store (the
+    loaded value stays live -> not fused); r0 = the stored value."""
+    a = Asm().ldx(8, 6, 1, 0).ld_map_value(2, fd, 0).ldx(8, 3, 2, 0).add64(3, "r6").stx(8, 2, 0, "r3")
+    a.mov64(7, "r3").mov64(0, "r7").exit()
+    return a.assemble()
+
+
 def test_ordered_mode_matches_sequential(fresh_oracle, fresh_runtime):
     """A last-writer-wins program (plain store of packet bytes into a shared
     map value) is order dependent: EBPF_BATCH_ORDERED reproduces the
     reference's sequential result exactly."""
     po, dev = fresh_oracle, fresh_runtime
     (om,), (dm,) = make_maps([(isa.BPF_MAP_TYPE_ARRAY, 4, 8, 1)], po, dev)
-    a = Asm().ldx(8, 6, 1, 0).ld_map_value(2, dm.fd, 0).ldx(8, 3, 2, 0).add64(3, "r6").stx(8, 2, 0, "r3")
-    a.mov64(7, "r3").mov64(0, "r7").exit()  # loaded value stays live -> not fused
-    code = a.assemble()
+    code = last_writer_prog(dm.fd)
     units = gen.sm64(3, np.arange(500, dtype=np.uint64)).view(np.uint8).reshape(500, 8)
     o, _, d, _, failed = _raw_both(po, dev, code, units, 8, flags=dev.BATCH_SYNC | dev.BATCH_ORDERED)
     assert failed == 0
@@ -387,15 +393,21 @@ def test_staged_typed_accesses(fresh_oracle, fresh_runtime, stride, n):
     np.testing.assert_array_equal(ds, os_)
 
 
-def test_staged_raw_slot_accesses(fresh_oracle, fresh_runtime):
-    """RAW units (r1 = the slot itself): slot-typed accesses read the staged
-    copy and see earlier stores."""
-    po, dev = fresh_oracle, fresh_runtime
+def staged_raw_prog():
+    """Loads of every size from the first 64 B of the unit, a store, a load
+    that sees it and a second store."""
     a = Asm().mov64(0, 0)
     for sz, off in [(8, 0), (4, 12), (2, 30), (1, 63)]:
         a.ldx(sz, 3, 1, off).alu64("add", 0, "r3")
     a.stx(4, 1, 12, "r0").ldx(4, 3, 1, 12).alu64("xor", 0, "r3").stx(8, 1, 40, "r0").exit()
-    code = a.assemble()
+    return a.assemble()
+
+
+def test_staged_raw_slot_accesses(fresh_oracle, fresh_runtime):
+    """RAW units (r1 = the slot itself): slot-typed accesses read the staged
+    copy and see earlier stores."""
+    po, dev = fresh_oracle, fresh_runtime
+    code = staged_raw_prog()
     n = 4000
     units = gen.xdp_packets(n, stride=64, seed=5)
     ovm = po.OracleVM()
