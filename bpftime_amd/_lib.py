@@ -72,6 +72,12 @@ class XdpCompleteArgs(C.Structure):  # include/bpftime_amd.h struct bpftime_amd_
                 ("gather_count", C.c_void_p), ("gather_skipped", C.c_void_p), ("host_gather", u32p)]
 
 
+class MapDumpArgs(C.Structure):  # include/bpftime_amd.h struct bpftime_amd_map_dump_args
+    _fields_ = [("fd", C.c_int), ("flags", C.c_uint32), ("start", C.c_uint64), ("cap", C.c_uint64),
+                ("keys", C.c_void_p), ("values", C.c_void_p), ("count", C.c_uint64), ("next", C.c_uint64),
+                ("end", C.c_uint64)]
+
+
 class PerfEvent(C.Structure):
     """struct bpftime_amd_perf_event (include/bpftime_amd.h)"""
     _fields_ = [("type", C.c_int), ("pid", C.c_int), ("enabled", C.c_int), ("tracepoint_id", C.c_int32),
@@ -194,6 +200,9 @@ SIGNATURES = [
     ("bpftime_amd_xdp_complete_from_batch", C.c_int, [C.POINTER(EbpfBatch), C.POINTER(XdpCompleteArgs)]),
     ("bpftime_amd_xdp_complete_tile", C.c_uint32, []),
     ("bpftime_amd_xdp_complete_scan_tiles", C.c_uint32, []),
+    ("bpftime_amd_map_dump", C.c_int, [C.POINTER(MapDumpArgs)]),
+    ("bpftime_amd_map_dump_tile", C.c_uint32, []),
+    ("bpftime_amd_map_dump_scan_tiles", C.c_uint32, []),
     ("bpftime_amd_enable_trace_printk", C.c_int, [C.c_int]),
     ("bpftime_amd_trace_read", C.c_int64, [C.POINTER(TraceLine), C.c_uint64, C.c_void_p, C.c_uint64, u64p]),
     ("bpftime_amd_syscall_attach", C.c_int, [C.c_int, C.c_int64]),

@@ -160,6 +160,9 @@ void bpftime_amd_reset(void) {
   syscall_detach_all();  // the link-made attachments and the direct ones
   uprobe_detach_all();
   if (r.d_maptab) hipMemset(r.d_maptab, 0, (sizeof(DMap) + sizeof(DPerf)) * kMaxFds);
+  if (r.dump_buf) hipFree(r.dump_buf);  // (bpftime_amd_map_dump's calls are synchronous: nothing uses it)
+  r.dump_buf = nullptr;
+  r.dump_bytes = 0;
   r.perf_dirty = false;  // (no perf record is left, and the table says so)
   r.arena_used = 0;
   r.trace_printk_on = false;

@@ -170,6 +170,11 @@ struct Runtime {
   // compacts tombstone-heavy LRU tables now and then; returns the launch's
   // stamp sequence (0 on failure)
   uint64_t prepare_lru();
+  // bpftime_amd_map_dump's scratch and staging (map_dump.cpp): one device
+  // buffer, replaced by a larger one when a call needs more, used under mu,
+  // freed by bpftime_amd_reset
+  void *dump_buf = nullptr;
+  uint64_t dump_bytes = 0;
 };
 
 // hash lookup index upkeep for host-side writes (map_hash.cpp)

@@ -124,6 +124,42 @@ extern "C" long bpftime_amd_handle_sysbpf(int cmd, void *attr_, uint32_t size) {
       }
       return 0;
     }
+    // The reference's handler has no batch case; the contract is the kernel's
+    // uapi text (linux/bpf.h, "BPF_MAP_LOOKUP_BATCH"): in_batch NULL begins,
+    // out_batch continues, count is capacity in and elements out, and ENOENT
+    // says the map is exhausted -- with the last elements in the same call.
+    // The token is a u32, as the kernel's hash tables use (a bucket index).
+    case BPF_MAP_LOOKUP_BATCH:
+    case BPF_MAP_LOOKUP_AND_DELETE_BATCH: {
+      if (attr->batch.elem_flags || attr->batch.flags) {  // (no BPF_F_LOCK: maps here have no spin locks)
+        errno = EINVAL;
+        return -1;
+      }
+      struct bpftime_amd_map_dump_args a;
+      memset(&a, 0, sizeof(a));
+      a.fd = (int)attr->batch.map_fd;
+      a.flags = cmd == BPF_MAP_LOOKUP_AND_DELETE_BATCH ? BPFTIME_AMD_DUMP_DELETE : 0;
+      if (attr->batch.in_batch) {
+        uint32_t in;
+        memcpy(&in, (const void *)(uintptr_t)attr->batch.in_batch, 4);
+        a.start = in;
+      }
+      a.cap = attr->batch.count;
+      a.keys = (void *)(uintptr_t)attr->batch.keys;
+      a.values = (void *)(uintptr_t)attr->batch.values;
+      attr->batch.count = 0;
+      if (bpftime_amd_map_dump(&a) < 0) return -1;
+      attr->batch.count = (uint32_t)a.count;
+      if (attr->batch.out_batch) {
+        const uint32_t out = (uint32_t)a.next;
+        memcpy((void *)(uintptr_t)attr->batch.out_batch, &out, 4);
+      }
+      if (a.next == a.end) {
+        errno = ENOENT;
+        return -1;
+      }
+      return 0;
+    }
     case BPF_PROG_ATTACH:  // :723-735 -> bpftime_attach_perf_to_bpf(target perf fd, prog fd)
       return bpftime_attach_perf_to_bpf((int)attr->target_fd, (int)attr->attach_bpf_fd);
   }

@@ -14,8 +14,8 @@ from typing import Optional
 import numpy as np
 
 from . import isa
-from ._lib import (BpfLinkCreateArgs, BpfMapAttr, CallRecords, EbpfBatch, LaunchInfo, SysRecords, TraceLine,
-                   XdpCompleteArgs, lib)
+from ._lib import (BpfLinkCreateArgs, BpfMapAttr, CallRecords, EbpfBatch, LaunchInfo, MapDumpArgs, SysRecords,
+                   TraceLine, XdpCompleteArgs, lib)
 from ._lib import PerfEvent as PerfEventRec
 
 CTX_RAW, CTX_XDP, CTX_SYSCALL, CTX_SYSCALL_EXIT, CTX_UPROBE = 0, 1, 2, 3, 4
@@ -24,6 +24,7 @@ PT_REGS_BYTES = 168  # x86-64 struct pt_regs: the EBPF_CTX_UPROBE unit
 SYSCALL_RECORD, SYSCALL_RECORD_FULL, SYSCALL_RECORD_TIMED = 64, 96, 128  # include/bpftime_amd.h replay records
 DISPATCH_THREADS, DISPATCH_PROGRAMS = 0x100, 0x200  # dispatch plans (include/bpftime_amd.h)
 BATCH_SYNC, BATCH_ORDERED, BATCH_UNCHECKED, BATCH_SYS_NR, BATCH_TIMED = 0x1, 0x2, 0x4, 0x8, 0x10
+DUMP_DELETE = 1  # BPFTIME_AMD_DUMP_DELETE (include/bpftime_amd.h)
 
 
 class EbpfError(RuntimeError):
@@ -239,6 +240,31 @@ class Map:
 
     def count(self) -> int:
         return lib().bpftime_amd_map_count(self.fd)
+
+    def dump(self, cap: Optional[int] = None, start: int = 0, delete: bool = False, keys: bool = True,
+             values: bool = True):
+        """bpftime_amd_map_dump: up to `cap` entries (None: max_entries) from
+        the cursor `start`, in get_next_key order, compacted on the device.
+        -> (keys uint8[count, key_size], values uint8[count, user_value_size],
+        next, end); continue with start=next until next == end.  delete: the
+        returned entries are also removed (HASH / PERCPU_HASH).  keys / values
+        False: that output is not asked for (its array comes back with
+        count rows of width 0)."""
+        cap = self.max_entries if cap is None else int(cap)
+        vs = self.user_value_size
+        # (the library writes count <= cap entries; a huge cap is clipped to what the map can hold)
+        room = min(cap, max(self.max_entries, self.geometry()[0]))
+        k = np.empty((room, self.key_size if keys else 0), dtype=np.uint8)
+        v = np.empty((room, vs if values else 0), dtype=np.uint8)
+        a = MapDumpArgs(fd=self.fd, flags=DUMP_DELETE if delete else 0, start=start, cap=room,
+                        keys=k.ctypes.data if keys and room else None,
+                        values=v.ctypes.data if values and room else None)
+        C.set_errno(0)
+        if lib().bpftime_amd_map_dump(C.byref(a)) < 0:
+            e = EbpfError(_err())
+            e.errno = C.get_errno()
+            raise e
+        return k[:a.count], v[:a.count], a.next, a.end
 
     # BPF_MAP_TYPE_ARRAY_OF_MAPS (map_in_maps.hpp)
     def set_inner(self, index: int, inner, flags: int = 0) -> int:
@@ -826,6 +852,7 @@ class Event:
 # ---- bpf(2) commands (syscall_context.cpp:429-668) --------------------------
 BPF_MAP_CREATE, BPF_MAP_LOOKUP_ELEM, BPF_MAP_UPDATE_ELEM, BPF_MAP_DELETE_ELEM = 0, 1, 2, 3
 BPF_MAP_GET_NEXT_KEY, BPF_PROG_LOAD, BPF_MAP_FREEZE, BPF_LINK_CREATE = 4, 5, 22, 28
+BPF_MAP_LOOKUP_BATCH, BPF_MAP_LOOKUP_AND_DELETE_BATCH = 24, 25
 
 
 def sys_bpf(cmd: int, attr: bytearray) -> tuple:
@@ -849,6 +876,22 @@ def attr_map_elem(fd: int, key_addr: int, value_addr: int = 0, flags: int = 0) -
     a = bytearray(128)
     struct.pack_into("<IIQQQ", a, 0, fd, 0, key_addr, value_addr, flags)
     return a
+
+
+def attr_map_batch(fd: int, in_batch_addr: int, out_batch_addr: int, keys_addr: int, values_addr: int, count: int,
+                   elem_flags: int = 0, flags: int = 0) -> bytearray:
+    """union bpf_attr's `batch` member (BPF_MAP_LOOKUP_BATCH and its kin):
+    in_batch_addr 0 starts at the beginning; the handler writes the number of
+    entries returned back over count (batch_count reads it)."""
+    a = bytearray(128)
+    struct.pack_into("<QQQQIIQQ", a, 0, in_batch_addr, out_batch_addr, keys_addr, values_addr, count, fd,
+                     elem_flags, flags)
+    return a
+
+
+def batch_count(attr: bytearray) -> int:
+    """attr->batch.count of an attr_map_batch image."""
+    return struct.unpack_from("<I", attr, 32)[0]
 
 
 def attr_prog_load(prog_type: int, insns_addr: int, insn_cnt: int, name: str = "") -> bytearray:

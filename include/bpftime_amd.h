@@ -251,7 +251,14 @@ int64_t bpftime_amd_syscall_nr(const char *name);
  * kernel's union bpf_attr.  BPF_MAP_CREATE / BPF_PROG_LOAD / BPF_LINK_CREATE
  * return a new fd; lookups copy the value out (ENOENT when absent); update,
  * delete and get-next-key return the map operation's status; BPF_MAP_FREEZE
- * returns 0; other commands -1 with errno ENOTSUP. */
+ * returns 0; other commands -1 with errno ENOTSUP.
+ * BPF_MAP_LOOKUP_BATCH / BPF_MAP_LOOKUP_AND_DELETE_BATCH (attr->batch, the
+ * kernel's uapi contract; the reference's handler has no such case) run
+ * bpftime_amd_map_dump: the batch token is a u32 cursor, in_batch NULL starts
+ * at the beginning, *out_batch receives the next cursor, count is the
+ * capacity on input and the entries returned on output.  0, or -1 with ENOENT
+ * once the map is exhausted (count is still valid then and may be nonzero);
+ * nonzero elem_flags or flags EINVAL; the dump's own errno otherwise. */
 long bpftime_amd_handle_sysbpf(int cmd, void *attr, uint32_t size);
 
 /* ---- lddw helpers for the device VM (bpftime_shm.cpp:637-676) ---- */
@@ -817,6 +824,74 @@ int bpftime_amd_xdp_complete_from_batch(const struct ebpf_batch *batch, struct b
  * the tile-offset scan (for tests that pick sizes around them). */
 uint32_t bpftime_amd_xdp_complete_tile(void);
 uint32_t bpftime_amd_xdp_complete_scan_tiles(void);
+
+/* ---- map dump and drain (Map dump and drain; csrc/map_dump.cpp) ----
+ * Reads a map out in one call: up to `cap` entries from the cursor `start`,
+ * as dense key and value arrays, in the order a bpftime_map_get_next_key walk
+ * yields them.  A hash table is compacted on the device (csrc/map_dump.hip:
+ * count, scan, scatter; no atomics, no workgroup waiting on another), so only
+ * the entries returned cross to the caller.
+ *
+ * HASH, PERCPU_HASH, LRU_HASH: the cursor is a bucket index and end = the
+ * bucket count.  The entries are the live buckets (state word 1) with index >=
+ * start, in index order, the first cap of them; empty buckets and LRU
+ * tombstones are skipped.  next = the index of the first live bucket not
+ * returned, or end when every live bucket at or after start was returned.
+ * ARRAY, PERCPU_ARRAY: the cursor is an element index, end = max_entries; the
+ * entries are elements start .. start + cap - 1 (clipped at end), the keys
+ * their u32 indices; next = start + count.
+ * A value is the syscall side's view, bpftime_map_value_size_from_syscall(fd)
+ * bytes: for a per-CPU map all ncpu values, contiguous.
+ *
+ * keys / values may be host or device memory (the copy is hipMemcpyDefault)
+ * and either may be NULL: that output is skipped, the entries still count
+ * (and with BPFTIME_AMD_DUMP_DELETE are still deleted).  start == end returns
+ * 0 with count 0 and next = end; cap == 0 returns 0 with count 0 and next =
+ * start, without a launch.
+ *
+ * A plain dump changes nothing in the map: not the slots, not the element
+ * counter, not an LRU map's stamps (a dump is not a use, as the kernel's
+ * batch lookup refreshes no recency).
+ *
+ * BPFTIME_AMD_DUMP_DELETE (HASH, PERCPU_HASH): each returned entry's state
+ * word becomes 0 (key and value bytes stay), the element counter drops by
+ * count and the lookup index is invalidated; no launch that trusts its lookup
+ * cache is running by then.  The map is left exactly as count calls of
+ * bpftime_map_delete_elem on the returned keys leave it when each finds its key
+ * (last returned first: in bucket order a delete of an earlier bucket of a
+ * probe run can orphan a later key of the run, whose own delete then finds
+ * nothing; the drain clears exactly the buckets it returned).  On ARRAY /
+ * PERCPU_ARRAY it is EINVAL, as their delete.  On LRU_HASH it is ENOTSUP:
+ * tombstones, the tombstone counter and compaction stay with the map's own
+ * delete; drain an LRU map with bpftime_map_delete_elem.
+ *
+ * The call is synchronous: it takes the runtime lock and waits for the device
+ * first, so a batch on any stream has finished and its deferred counter adds
+ * are in the table.  Like every host-side map operation it must not race a
+ * batch launched meanwhile from another thread.
+ *
+ * 0, or -1 with errno and bpftime_amd_last_error: EINVAL (NULL args -- before
+ * anything else --, unknown flag bits, start > end, DELETE on an array),
+ * ENOENT (fd is no map), ENOTSUP (every other map type, naming the type; DELETE
+ * on LRU_HASH), ENOMEM / EIO (the device).  The checks of args, flags and fd
+ * need no device. */
+#define BPFTIME_AMD_DUMP_DELETE 1u /* also remove every entry returned */
+struct bpftime_amd_map_dump_args {
+  int fd;
+  uint32_t flags; /* 0 or BPFTIME_AMD_DUMP_DELETE; any other bit: EINVAL */
+  uint64_t start; /* in: cursor, 0 = from the beginning */
+  uint64_t cap;   /* in: entries keys / values have room for */
+  void *keys;     /* out: count * key_size bytes, dense; host or device memory; may be NULL */
+  void *values;   /* out: count * bpftime_map_value_size_from_syscall(fd) bytes, dense; may be NULL */
+  uint64_t count; /* out: entries returned (<= cap) */
+  uint64_t next;  /* out: cursor to pass as start to continue */
+  uint64_t end;   /* out: the cursor value that means "nothing left" */
+};
+int bpftime_amd_map_dump(struct bpftime_amd_map_dump_args *args);
+/* Buckets per workgroup tile of the dump kernels, and tiles per pass of the
+ * tile-offset scan (for tests that pick sizes around them). */
+uint32_t bpftime_amd_map_dump_tile(void);
+uint32_t bpftime_amd_map_dump_scan_tiles(void);
 
 /* ---- attach plugins (attach/base_attach_impl/base_attach_impl.hpp:24-71,
  * attach/simple_attach_impl/simple_attach_impl.cpp:7-55; csrc/attach.cpp) ----
